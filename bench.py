@@ -6,7 +6,11 @@ saturn_amd's own training stack: fused CDNA4 kernels for
 LayerNorm/RoPE/attention/CE/optimizer, bucketed flat-buffer DDP over RCCL.
 
 Contract (driver):
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result
+line; --dump-outputs DIR adds the last timed step's results as .npy files
+(inputs and init are seeded, so two builds can be compared output for
+output); --full is where anything beyond the headline figure belongs.
 For N>1 the driver launches via torch.distributed.run; ranks read
 RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the env.  Rank 0 prints ONE JSON
 line; `value` is whole-job samples/sec aggregated over all N GPUs;
@@ -26,6 +30,41 @@ import torch
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+LOGITS_SAMPLE = 1 << 20  # elements of the logits kept by --dump-outputs
+PARAM_SAMPLE = 4096  # elements kept per parameter tensor
+
+
+def _sample(t: torch.Tensor, n: int, g: torch.Generator) -> torch.Tensor:
+    """`t` flattened if it has at most `n` elements, else `n` of them at
+    indices drawn from `g` (fixed seed: the same indices in every run)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > n:
+        idx = torch.randint(0, flat.numel(), (n,), generator=g)
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu()
+
+
+def dump_outputs(out_dir: str, logits, loss, model) -> None:
+    """Write what the last timed step handed back to its caller: the loss,
+    the logits (absent under --hipgraph, where replay returns the loss only)
+    and the parameters as the optimizer left them.  Full logits and
+    parameters run to GBs, so fixed seeded samples are kept; float32 holds
+    every bf16/fp32 value exactly."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator(device="cpu").manual_seed(97)
+    arrays = {"loss": loss.detach().reshape(1).float().cpu()}
+    if logits is not None:
+        arrays["logits_sample"] = _sample(logits, LOGITS_SAMPLE, g)
+    arrays["params_sample"] = torch.cat(
+        [_sample(p, PARAM_SAMPLE, g) for p in model.parameters()]
+    )
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+    log(f"dumped {', '.join(sorted(arrays))} to {out_dir}")
 
 
 def main() -> None:
@@ -50,7 +89,24 @@ def main() -> None:
         help="use the offline-tuned hipBLASLt/rocBLAS GEMM algo table "
         "(tools/tunableop_gfx950.csv), tuning disabled at runtime",
     )
+    ap.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, write what the last timed step computed "
+        "(loss, a seeded sample of the logits and of the updated parameters) "
+        "as DIR/<name>.npy in float32",
+    )
+    ap.add_argument(
+        "--full",
+        action="store_true",
+        help="also run whatever the benchmark measures beyond the headline "
+        "figure; a plain run does only setup, warmup, the timed steps and "
+        "the result line (nothing extra is measured today)",
+    )
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(
@@ -156,18 +212,19 @@ def main() -> None:
                                                ddp=ddp)
         static_x.copy_(x)
 
-        def step() -> None:
-            graphed.replay()
+        def step():
+            return None, graphed.replay()
 
     else:
 
-        def step() -> None:
+        def step():
             logits = ddp(x)
             loss = loss_fn(logits, x)
             loss.backward()
             ddp.grad_sync()
             opt.step()
             ddp.zero_grad_buffers()
+            return logits, loss
 
     log(f"[rank {rank}] {n_params/1e9:.2f}B params; warmup {args.warmup} steps")
     for _ in range(args.warmup):
@@ -178,8 +235,11 @@ def main() -> None:
     if use_gpu:
         torch.cuda.synchronize()
     t0 = timer()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    # only the last step's results are held, so no step runs with the
+    # previous step's logits still allocated
+    logits, loss = step()
     if use_gpu:
         torch.cuda.synchronize()
     if world > 1:
@@ -192,6 +252,9 @@ def main() -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if use_gpu else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, logits, loss, model)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1000.0

@@ -58,3 +58,45 @@ def test_bench_single_process_defaults():
         [l for l in out.stdout.splitlines() if l.startswith("{")][0]
     )
     assert d["n_gpus"] == 1 and d["higher_is_better"] is True
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's results as float32 .npy
+    (well under 64 MB), identically from run to run; --full is accepted and
+    the result line keeps its fields and honours --steps.  This is the CPU
+    path (conftest hides devices from unmarked tests), whose arithmetic is
+    order-stable, so equal inputs must give bit-equal dumps."""
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--steps", "2",
+             "--warmup", "1", "--layers", "1", "--seq", "32", "--batch", "2",
+             "--dump-outputs", str(d)] + extra,
+            cwd=REPO,
+            capture_output=True,
+            text=True,
+            timeout=600,
+        )
+        assert out.returncode == 0, out.stderr[-2000:]
+        json_lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(json_lines) == 1, out.stdout
+        r = json.loads(json_lines[0])
+        assert r["steps"] == 2 and r["ms_per_step"] > 0
+        assert r["dtype"] == "fp32"
+        # samples/s = per-GPU batch / seconds per timed step
+        assert abs(r["value"] - 2 * 1000.0 / r["ms_per_step"]) < 1e-6 * r["value"]
+        files = sorted(os.listdir(d))
+        assert files == ["logits_sample.npy", "loss.npy", "params_sample.npy"]
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 1000 * 1000
+        assert all(np.isfinite(a).all() for a in arrays.values())
+        assert arrays["loss.npy"].shape == (1,)
+        # batch 2 x seq 32 x vocab exceeds the cap: a fixed-size sample
+        assert arrays["logits_sample.npy"].shape == (1 << 20,)
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

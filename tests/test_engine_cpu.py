@@ -180,10 +180,14 @@ def test_orchestrate_gives_up_after_max_retries(save_dir, library_path):
                     max_task_retries=1)
 
 
-def test_orchestrate_four_gpu_gang(save_dir, library_path):
+def test_orchestrate_four_gpu_gang(save_dir, library_path, machine_gpu_count):
     """A 4-process gloo gang through the full pipeline (the driver's scale
     bench runs world 4/8 on hardware; this pins the rendezvous + gang
     binding shape beyond world 2)."""
+    if 0 < machine_gpu_count < 4:
+        # the engine's launcher hands each gang its devices itself, so on a
+        # GPU machine the ranks bind one device each
+        pytest.skip(f"needs 4 GPUs (or none), found {machine_gpu_count}")
     from saturn_amd import HParams, Strategy, Task, orchestrate
     from saturn_amd.executors.ddp import DDPExecutor
     from saturn_amd.models import get_mlp_dataloader, get_mlp_model, mse_loss
