@@ -22,6 +22,7 @@ from saturn_amd.ops.functional import (
     fused_cross_entropy,
     fused_swiglu,
 )
+from saturn_amd.ops.moe import moe_combine, moe_permute, moe_route, moe_sort
 
 
 @dataclass
@@ -62,22 +63,75 @@ def route(router: nn.Linear, x_flat: torch.Tensor, top_k: int):
     """Top-k routing: returns (weights [N,k] in x.dtype, expert ids [N,k]).
 
     Softmax in fp32 over all experts, then renormalized over the chosen k
-    (Mixtral semantics).
+    (Mixtral semantics).  On GPU this is one ``moe_route`` kernel each way
+    (int32 ids, ties to the lower expert index); on CPU the torch chain.
     """
-    logits = router(x_flat).float()
+    logits = router(x_flat)
+    if logits.is_cuda:
+        return moe_route(logits, top_k, x_flat.dtype)
+    logits = logits.float()
     probs = torch.softmax(logits, dim=-1)
     topv, topi = probs.topk(top_k, dim=-1)
     topv = topv / topv.sum(dim=-1, keepdim=True)
     return topv.to(x_flat.dtype), topi
 
 
+def moe_experts_forward(xf, weights, ids, experts, dispatch):
+    """The expert stage of one MoE layer, given a routing result: returns
+    ``out[t] = sum_j weights[t,j] * experts[ids[t,j]](xf[t])`` as [N, hidden].
+
+    ``dispatch="loop"`` is the reference: one ``nonzero`` (a host sync) and
+    one out-of-place ``index_add`` (a full copy of the output) per expert.
+
+    ``dispatch="fused"`` sorts the (token, slot) pairs by expert once
+    (``moe_sort``), gathers the rows into expert order (``moe_permute``),
+    runs each expert on its contiguous slice and reduces each token's k rows
+    in fp32 (``moe_combine``).  It keeps ONE host sync per layer (the
+    ``counts.tolist()`` that sizes the slices), so like the loop path it
+    cannot be captured into a hipGraph.
+    """
+    if dispatch == "loop":
+        out = torch.zeros_like(xf)
+        for e, expert in enumerate(experts):
+            tok, slot = (ids == e).nonzero(as_tuple=True)
+            if tok.numel() == 0:
+                continue
+            out = out.index_add(
+                0, tok, expert(xf[tok]) * weights[tok, slot].unsqueeze(-1)
+            )
+        return out
+    if dispatch != "fused":
+        raise ValueError(f"unknown MoE dispatch {dispatch!r}")
+    order, pos, counts = moe_sort(ids, len(experts))
+    xs = moe_permute(xf, order, pos)
+    sizes = counts.tolist()  # the only host sync of the layer
+    pieces = [
+        expert(rows)
+        for expert, rows, n in zip(experts, xs.split(sizes), sizes)
+        if n
+    ]
+    return moe_combine(torch.cat(pieces), weights, pos)
+
+
+def resolve_dispatch(dispatch, x: torch.Tensor) -> str:
+    """``None`` = auto: the fused kernels on GPU, the loop on CPU."""
+    if dispatch is None:
+        return "fused" if x.is_cuda else "loop"
+    return dispatch
+
+
 class MoEMLP(nn.Module):
-    """Dense-dispatch reference MoE layer (single process, exact)."""
+    """Dense-dispatch reference MoE layer (single process, exact).
+
+    ``dispatch``: ``"loop"``, ``"fused"`` or ``None`` (auto: ``"fused"`` on
+    GPU, ``"loop"`` on CPU) — see :func:`moe_experts_forward`.
+    """
 
     def __init__(self, cfg: MixtralConfig):
         super().__init__()
         self.n_expert = cfg.n_expert
         self.top_k = cfg.top_k
+        self.dispatch = None
         self.router = nn.Linear(cfg.n_embd, cfg.n_expert, bias=False)
         self.experts = nn.ModuleList(MoEExpert(cfg) for _ in range(cfg.n_expert))
 
@@ -85,14 +139,8 @@ class MoEMLP(nn.Module):
         B, T, E = x.shape
         xf = x.reshape(-1, E)
         weights, topi = route(self.router, xf, self.top_k)
-        out = torch.zeros_like(xf)
-        for e, expert in enumerate(self.experts):
-            tok, slot = (topi == e).nonzero(as_tuple=True)
-            if tok.numel() == 0:
-                continue
-            out = out.index_add(
-                0, tok, expert(xf[tok]) * weights[tok, slot].unsqueeze(-1)
-            )
+        out = moe_experts_forward(xf, weights, topi, self.experts,
+                                  resolve_dispatch(self.dispatch, xf))
         return out.reshape(B, T, E)
 
 

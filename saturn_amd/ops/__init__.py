@@ -46,3 +46,21 @@ def require_ext():
             f"(import error: {_ext_err})"
         )
     return ext
+
+
+# MoE routing / dispatch ops (K13); imported last: ops.moe needs require_ext
+from saturn_amd.ops.moe import (  # noqa: E402
+    moe_combine,
+    moe_permute,
+    moe_route,
+    moe_sort,
+)
+
+__all__ = [
+    "has_ext",
+    "require_ext",
+    "moe_route",
+    "moe_sort",
+    "moe_permute",
+    "moe_combine",
+]

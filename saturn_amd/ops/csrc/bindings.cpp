@@ -39,6 +39,16 @@ at::Tensor embed_fwd(at::Tensor weight, at::Tensor idx);
 at::Tensor embed_bwd(at::Tensor dout, at::Tensor idx, long vocab);
 at::Tensor dropout_fwd(at::Tensor x, double p, long seed);
 at::Tensor dropout_bwd(at::Tensor dout, double p, long seed);
+std::vector<at::Tensor> moe_route_fwd(at::Tensor logits, int64_t top_k,
+                                      at::ScalarType out_dtype);
+at::Tensor moe_route_bwd(at::Tensor logits, at::Tensor ids,
+                         at::Tensor dweights);
+std::vector<at::Tensor> moe_sort(at::Tensor ids, int64_t n_expert);
+at::Tensor moe_permute_fwd(at::Tensor x, at::Tensor order, int64_t top_k);
+at::Tensor moe_permute_bwd(at::Tensor dxs, at::Tensor pos);
+at::Tensor moe_combine_fwd(at::Tensor y, at::Tensor weights, at::Tensor pos);
+std::vector<at::Tensor> moe_combine_bwd(at::Tensor dout, at::Tensor y,
+                                        at::Tensor weights, at::Tensor pos);
 }  // namespace samd
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -67,4 +77,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embed_bwd", &samd::embed_bwd, "embedding scatter-add backward");
   m.def("dropout_fwd", &samd::dropout_fwd, "counter-based fused dropout");
   m.def("dropout_bwd", &samd::dropout_bwd, "dropout backward (mask recompute)");
+  m.def("moe_route_fwd", &samd::moe_route_fwd,
+        "MoE softmax + top-k + renormalise (ties to the lower expert)");
+  m.def("moe_route_bwd", &samd::moe_route_bwd, "MoE routing backward");
+  m.def("moe_sort", &samd::moe_sort,
+        "stable counting sort of (token, slot) pairs by expert");
+  m.def("moe_permute_fwd", &samd::moe_permute_fwd,
+        "gather token rows into expert order");
+  m.def("moe_permute_bwd", &samd::moe_permute_bwd,
+        "sum each token's k permuted rows");
+  m.def("moe_combine_fwd", &samd::moe_combine_fwd,
+        "weighted sum of each token's k expert rows");
+  m.def("moe_combine_bwd", &samd::moe_combine_bwd,
+        "combine backward: dy and fp32 dweights");
 }

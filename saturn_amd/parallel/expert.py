@@ -35,7 +35,12 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from saturn_amd.models.mixtral import MoEMLP, route
+from saturn_amd.models.mixtral import (
+    MoEMLP,
+    moe_experts_forward,
+    resolve_dispatch,
+    route,
+)
 
 
 def _a2a_impl(x: torch.Tensor, out_splits: List[int], in_splits: List[int],
@@ -102,6 +107,7 @@ class DistributedMoE(nn.Module):
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.n_expert = moe.n_expert
         self.top_k = moe.top_k
+        self.dispatch = getattr(moe, "dispatch", None)
         if self.n_expert % self.world != 0:
             raise ValueError(
                 f"n_expert {self.n_expert} not divisible by world {self.world}"
@@ -118,15 +124,11 @@ class DistributedMoE(nn.Module):
         xf = x.reshape(-1, E)
         weights, topi = route(self.router, xf, self.top_k)
         if self.world == 1:
-            out = torch.zeros_like(xf)
-            for i, expert in enumerate(self.local_experts):
-                tok, slot = (topi == i).nonzero(as_tuple=True)
-                if tok.numel():
-                    out = out.index_add(
-                        0, tok, expert(xf[tok]) * weights[tok, slot].unsqueeze(-1)
-                    )
+            out = moe_experts_forward(xf, weights, topi, self.local_experts,
+                                      resolve_dispatch(self.dispatch, xf))
             return out.reshape(B, T, E)
 
+        # ops.moe.moe_sort returns exactly this `order` and `counts`
         flat_e = topi.reshape(-1)  # pair p = token p // k, slot p % k
         order = torch.argsort(flat_e, stable=True)
         pair_tok = order // self.top_k

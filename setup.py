@@ -30,6 +30,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "swiglu.hip"),
         os.path.join(CSRC, "embedding.hip"),
         os.path.join(CSRC, "dropout.hip"),
+        os.path.join(CSRC, "moe.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
