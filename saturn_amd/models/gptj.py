@@ -18,6 +18,7 @@ datasets; BASELINE.md mandates synthetic + random init).
 from __future__ import annotations
 
 
+import os
 from dataclasses import dataclass
 
 import torch
@@ -33,6 +34,8 @@ from saturn_amd.ops.functional import (
     rope_tables,
     FusedDropout,
     FusedEmbedding,
+    gptj_mlp,
+    mlp_fused_supported,
 )
 
 
@@ -97,7 +100,34 @@ class GPTJMLP(nn.Module):
         self.fc_in = nn.Linear(E, 4 * E)
         self.fc_out = nn.Linear(4 * E, E)
 
+    @staticmethod
+    def _plain_linear(m) -> bool:
+        # exactly nn.Linear (tensor parallelism swaps in Column/RowParallel
+        # children) and no hooks that a direct use of the weights would skip
+        return type(m) is nn.Linear and not (
+            m._forward_hooks
+            or m._forward_pre_hooks
+            or m._backward_hooks
+            or m._backward_pre_hooks
+        )
+
+    def _use_fused(self, x) -> bool:
+        if os.environ.get("SAMD_MLP_FUSED", "1") == "0":
+            return False
+        fi, fo = self.fc_in, self.fc_out
+        return (
+            x.is_cuda
+            and self._plain_linear(fi)
+            and self._plain_linear(fo)
+            and mlp_fused_supported(x, fi.weight, fi.bias, fo.weight, fo.bias)
+        )
+
     def forward(self, x):
+        if self._use_fused(x):
+            # same forward; the backward (mlp_bwd.hip) fuses the activation
+            # backward with the bias grads and the TN weight-grad operands
+            fi, fo = self.fc_in, self.fc_out
+            return gptj_mlp(x, fi.weight, fi.bias, fo.weight, fo.bias)
         return self.fc_out(fused_gelu(self.fc_in(x)))
 
 

@@ -49,6 +49,12 @@ at::Tensor moe_permute_bwd(at::Tensor dxs, at::Tensor pos);
 at::Tensor moe_combine_fwd(at::Tensor y, at::Tensor weights, at::Tensor pos);
 std::vector<at::Tensor> moe_combine_bwd(at::Tensor dout, at::Tensor y,
                                         at::Tensor weights, at::Tensor pos);
+std::vector<at::Tensor> mlp_act_bwd(at::Tensor d_act, at::Tensor pre,
+                                    bool want_dT, bool want_aT);
+std::vector<at::Tensor> transpose_colsum(at::Tensor x, bool want_sum);
+std::vector<at::Tensor> mlp_bwd(at::Tensor g, at::Tensor h, at::Tensor pre,
+                                at::Tensor W_in, at::Tensor W_out,
+                                bool use_tn_in, bool use_tn_out);
 }  // namespace samd
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -90,4 +96,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "weighted sum of each token's k expert rows");
   m.def("moe_combine_bwd", &samd::moe_combine_bwd,
         "combine backward: dy and fp32 dweights");
+  m.def("mlp_act_bwd", &samd::mlp_act_bwd,
+        "GELU backward + transposed d_pre / gelu(pre) + fp32 bias grad",
+        py::arg("d_act"), py::arg("pre"), py::arg("want_dT") = true,
+        py::arg("want_aT") = true);
+  m.def("transpose_colsum", &samd::transpose_colsum,
+        "bf16 transpose with optional fp32 column sums");
+  m.def("mlp_bwd", &samd::mlp_bwd,
+        "GPT-J MLP backward with TN-layout weight gradients");
 }

@@ -13,29 +13,11 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "gelu_math.h"  // gelu_f / dgelu_f, shared with mlp_bwd.hip
 
 namespace samd {
 
 typedef __attribute__((ext_vector_type(8))) short short8v_g;
-
-__device__ __forceinline__ float tanh_fast(float u) {
-  return 1.f - 2.f / (__expf(2.f * u) + 1.f);
-}
-
-constexpr float GK = 0.7978845608028654f;  // sqrt(2/pi)
-constexpr float GC = 0.044715f;
-
-__device__ __forceinline__ float gelu_f(float x) {
-  const float t = tanh_fast(GK * (x + GC * x * x * x));
-  return 0.5f * x * (1.f + t);
-}
-
-__device__ __forceinline__ float dgelu_f(float x) {
-  const float u = GK * (x + GC * x * x * x);
-  const float t = tanh_fast(u);
-  const float du = GK * (1.f + 3.f * GC * x * x);
-  return 0.5f * (1.f + t) + 0.5f * x * (1.f - t * t) * du;
-}
 
 template <typename T, bool BWD>
 __global__ void gelu_kernel(const T* __restrict__ x, const T* __restrict__ dy,

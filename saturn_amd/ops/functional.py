@@ -8,6 +8,7 @@ numerics tests compare the two paths (tests/test_ops_gpu.py).
 
 from __future__ import annotations
 
+import os
 from typing import Tuple
 
 import torch
@@ -329,6 +330,80 @@ def fused_gelu(x: torch.Tensor) -> torch.Tensor:
     if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16):
         return _GeluFn.apply(x)
     return torch.nn.functional.gelu(x, approximate="tanh")
+
+
+# ---------------------------------------------------------------------------
+# GPT-J MLP with a fused backward (mlp_bwd.hip): the activation backward also
+# writes the transposed operands and the bias gradient, so the two weight
+# gradients can run as TN GEMMs (F.linear(dY^T, X^T)) instead of NT.
+# ---------------------------------------------------------------------------
+# Per-site default of the TN route, from profiles/r03_wgrad_layout_probe.txt;
+# SAMD_MLP_TN_IN / SAMD_MLP_TN_OUT = 0|1 override it for A/B runs.
+_MLP_TN_DEFAULT = {"in": True, "out": True}
+
+
+def _mlp_tn(site: str) -> bool:
+    v = os.environ.get("SAMD_MLP_TN_" + site.upper())
+    return _MLP_TN_DEFAULT[site] if v is None else v != "0"
+
+
+def mlp_fused_supported(x, w_in, b_in, w_out, b_out) -> bool:
+    """Inputs ``ext.mlp_bwd`` accepts: CUDA bf16, biases present, token count
+    and both widths multiples of 8 (whole 16-byte vectors either way round)."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() >= 2):
+        return False
+    if b_in is None or b_out is None:
+        return False
+    if any(t.dtype != torch.bfloat16 or not t.is_cuda
+           for t in (w_in, b_in, w_out, b_out)):
+        return False
+    E = x.shape[-1]
+    M = x.numel() // E if E else 0
+    F_ = w_in.shape[0]
+    return (
+        M > 0
+        and w_in.shape == (F_, E)
+        and w_out.shape == (E, F_)
+        and M % 8 == 0
+        and E % 8 == 0
+        and F_ % 8 == 0
+    )
+
+
+class _GPTJMlpFn(torch.autograd.Function):
+    """fc_out(gelu(fc_in(h))).  The forward is the unfused path's three
+    calls; it saves h and the pre-activation but not gelu(pre), which the
+    backward regenerates (transposed) inside the activation-backward pass."""
+
+    @staticmethod
+    def forward(ctx, h, w_in, b_in, w_out, b_out):
+        ext = require_ext()
+        pre = F.linear(h, w_in, b_in).contiguous()
+        out = F.linear(ext.gelu_fwd(pre), w_out, b_out)
+        ctx.save_for_backward(h, pre, w_in, w_out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ext = require_ext()
+        h, pre, w_in, w_out = ctx.saved_tensors
+        E = h.shape[-1]
+        dh, dw_in, db_in, dw_out, db_out = ext.mlp_bwd(
+            g.contiguous().view(-1, E),
+            h.contiguous().view(-1, E),
+            pre.view(-1, pre.shape[-1]),
+            w_in.contiguous(),
+            w_out.contiguous(),
+            _mlp_tn("in"),
+            _mlp_tn("out"),
+        )
+        return dh.view(h.shape), dw_in, db_in, dw_out, db_out
+
+
+def gptj_mlp(h, w_in, b_in, w_out, b_out):
+    """GPT-J MLP through the fused backward; callers check
+    ``mlp_fused_supported`` first."""
+    return _GPTJMlpFn.apply(h, w_in, b_in, w_out, b_out)
 
 
 class _SwigluFn(torch.autograd.Function):

@@ -31,6 +31,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "embedding.hip"),
         os.path.join(CSRC, "dropout.hip"),
         os.path.join(CSRC, "moe.hip"),
+        os.path.join(CSRC, "mlp_bwd.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
