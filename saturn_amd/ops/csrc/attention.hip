@@ -527,6 +527,62 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
 
 
 // ---------------------------------------------------------------------------
+// Dispatch rules.  Each environment switch is read once per process; the
+// predicates below are the ONLY place a (T, D) -> kernel decision is made:
+// the launchers and attn_dispatch() (which reports the decision to the
+// tests) both go through them.
+// ---------------------------------------------------------------------------
+static bool env_is(const char* name, char c) {
+  const char* e = getenv(name);
+  return e && e[0] == c;
+}
+// v2 structure (swapped 32x32 MFMAs, in-register P): default ON for the
+// shapes it supports (+40% measured at D=128/64); SAMD_ATTN_V2=0 forces
+// the v1 16x16 structure.
+static bool sw_v2() {
+  static const bool v = !env_is("SAMD_ATTN_V2", '0');
+  return v;
+}
+// default ON for D<=128 (measured +2-11% bwd across shapes);
+// SAMD_ATTN_BWD_TR16=0 reverts to scalar gathers
+static bool sw_tr16() {
+  static const bool v = !env_is("SAMD_ATTN_BWD_TR16", '0');
+  return v;
+}
+static bool sw_dq_gkv() {
+  static const bool v = env_is("SAMD_ATTN_DQ_GKV", '1');
+  return v;
+}
+// V tile from L2 instead of LDS at D<=128 (SAMD_ATTN_BWD_VL2=1): trades
+// per-q-tile L2 re-reads for 62->45 KB LDS/block (3 blocks/CU scalar path)
+static bool sw_vl2() {
+  static const bool v = env_is("SAMD_ATTN_BWD_VL2", '1');
+  return v;
+}
+// D=256 would spill at the v2 structure (256 VGPRs + 53); v1 handles it
+static bool fwd_is_v2(int T, int D) {
+  return sw_v2() && T % 128 == 0 && D <= 128;
+}
+static bool bwd_is_tr16(int D) { return sw_tr16() && D <= 128; }
+static bool bwd_is_vl2(int D) { return sw_vl2() && D <= 128; }
+static bool dq_is_gkv(int D) { return sw_dq_gkv() && D > 128; }
+
+// The kernel instantiations attn_fwd / attn_bwd launch for a padded T and
+// a head size D in this process, space-separated.
+std::string attn_dispatch(int64_t T, int64_t D) {
+  TORCH_CHECK(T > 0 && T % QBLK == 0, "attn_dispatch: T must be a multiple of 64");
+  TORCH_CHECK(D == 64 || D == 128 || D == 256, "attn_dispatch: D in {64,128,256}");
+  const int t = (int)T, d = (int)D;
+  const std::string ds = std::to_string(d);
+  const bool gkv = dq_is_gkv(d);
+  return std::string(fwd_is_v2(t, d) ? "attn_fwd_v2_kernel<" : "attn_fwd_kernel<") +
+         ds + "> attn_delta_kernel<" + ds + "> attn_bwd_kernel<" + ds + "," +
+         (bwd_is_tr16(d) ? "1," : "0,") + (bwd_is_vl2(d) ? "1>" : "0>") +
+         " attn_dq_kernel<" + ds + "," +
+         (!gkv && bwd_is_tr16(d) ? "1," : "0,") + (gkv ? "1>" : "0>");
+}
+
+// ---------------------------------------------------------------------------
 // Host wrapper
 // ---------------------------------------------------------------------------
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
@@ -559,15 +615,7 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   auto stream = at::hip::getCurrentHIPStream();
   const float scale = 1.f / sqrtf((float)D);
 
-  // v2 structure (swapped 32x32 MFMAs, in-register P): default ON for the
-  // shapes it supports (+40% measured at D=128/64); SAMD_ATTN_V2=0 forces
-  // the v1 16x16 structure.
-  static const bool use_v2 = [] {
-    const char* e = getenv("SAMD_ATTN_V2");
-    return !(e && e[0] == '0');
-  }();
-  // D=256 would spill at this structure (256 VGPRs + 53); v1 handles it
-  if (use_v2 && T % 128 == 0 && D <= 128) {
+  if (fwd_is_v2(T, D)) {
     dim3 grid2(B * H, T / 128), block2(256);
 #define LAUNCH_V2(DD)                                                        \
     do {                                                                     \
@@ -1129,22 +1177,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
   auto stream = at::hip::getCurrentHIPStream();
   const float scale = 1.f / sqrtf((float)D);
   dim3 grid(B * H, T / KB), block(256);
-  // default ON for D<=128 (measured +2-11% bwd across shapes; numerics
-  // validated both ways); SAMD_ATTN_BWD_TR16=0 reverts to scalar gathers
-  static const bool use_tr16 = [] {
-    const char* e = getenv("SAMD_ATTN_BWD_TR16");
-    return !(e && e[0] == '0');
-  }();
-  static const bool use_dq_gkv = [] {
-    const char* e = getenv("SAMD_ATTN_DQ_GKV");
-    return e && e[0] == '1';
-  }();
-  // V tile from L2 instead of LDS at D<=128 (SAMD_ATTN_BWD_VL2=1): trades
-  // per-q-tile L2 re-reads for 62->45 KB LDS/block (3 blocks/CU scalar path)
-  static const bool use_vl2 = [] {
-    const char* e = getenv("SAMD_ATTN_BWD_VL2");
-    return e && e[0] == '1';
-  }();
+  // kernel variants: see the dispatch rules above attn_fwd (numerics of
+  // every switch setting are checked by tests/test_attention_gpu.py)
 
 #define BWD_ARGS                                                             \
     stream.stream(),                                                         \
@@ -1175,7 +1209,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
        SLOWER at D=256 (612 vs 525 us at the GPT-J bench shape: the L2   \
        re-reads cost more than the occupancy gains) — kept as an opt-in  \
        probe only */                                                       \
-    const bool gkv = use_dq_gkv && DD > 128;                                 \
+    const bool gkv = dq_is_gkv(DD);                                          \
     size_t SH_DQ = gkv ? sizeof(AttnDqLds<DD, true>)                         \
                        : sizeof(AttnDqLds<DD, false>);                       \
     static bool dq_attr_##DD = [] {                                          \
@@ -1204,7 +1238,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                            T, H, Hkv, scale, causal ? 1 : 0, (int)kv_len,   \
                            str_of(dout), str_of(q), str_of(k), str_of(v),    \
                            str_of(dq));                                      \
-      else if (use_tr16 && DD <= 128)                                        \
+      else if (bwd_is_tr16(DD))                                              \
         hipLaunchKernelGGL((attn_dq_kernel<DD, true, false>), qgrid,         \
                            qblock, SH_DQ, stream.stream(),                   \
                            reinterpret_cast<const unsigned short*>(dout.data_ptr()), \
@@ -1229,8 +1263,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                            str_of(dout), str_of(q), str_of(k), str_of(v),    \
                            str_of(dq));                                      \
     }                                                                        \
-    const bool tr = use_tr16 && DD <= 128;                                   \
-    const bool vl2 = use_vl2 && DD <= 128;                                   \
+    const bool tr = bwd_is_tr16(DD);                                         \
+    const bool vl2 = bwd_is_vl2(DD);                                         \
     constexpr size_t SH_V = sizeof(AttnBwdLds<DD, (DD <= 128)>);             \
     constexpr size_t SH_N = sizeof(AttnBwdLds<DD, false>);                   \
     size_t shmem = vl2 ? SH_N : SH_V;                                        \

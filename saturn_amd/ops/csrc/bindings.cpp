@@ -31,6 +31,7 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  at::Tensor v, at::Tensor o, at::Tensor lse,
                                  bool causal, int64_t kv_len);
+std::string attn_dispatch(int64_t T, int64_t D);
 at::Tensor add3(at::Tensor a, at::Tensor b, at::Tensor c);
 at::Tensor swiglu_fwd(at::Tensor gate, at::Tensor up);
 std::vector<at::Tensor> swiglu_bwd(at::Tensor dout, at::Tensor gate,
@@ -72,6 +73,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &samd::attn_fwd, "fused flash attention forward",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
         py::arg("kv_len") = -1);
+  m.def("attn_dispatch", &samd::attn_dispatch,
+        "kernel instantiations attn_fwd/attn_bwd launch for (padded T, D)",
+        py::arg("T"), py::arg("D"));
   m.def("attn_bwd", &samd::attn_bwd, "fused flash attention backward",
         py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o"), py::arg("lse"), py::arg("causal"),

@@ -85,10 +85,16 @@ def _kernel_supported(q) -> bool:
 def _dense_rows(t):
     """The kernels address arbitrary (B, H, T) strides but need a dense,
     16-B-aligned innermost dim — transposed views of the model's [B,T,H,D]
-    projections qualify, so no copies in the common path."""
-    if t.stride(-1) == 1 and t.stride(2) % 8 == 0:
+    projections qualify, so no copies in the common path.  Every row must
+    start on a 16-B boundary: a view that starts off one (a column slice at
+    an offset that is no multiple of 8 elements), or whose batch or head
+    stride is no multiple of 8, is copied too.  The copy is a clone into
+    fresh (aligned) storage: .contiguous() would hand back an already
+    contiguous tensor that merely starts at a misaligned offset."""
+    if (t.stride(-1) == 1 and t.storage_offset() % 8 == 0
+            and all(s % 8 == 0 for s in t.stride()[:-1])):
         return t
-    return t.contiguous()
+    return t.clone(memory_format=torch.contiguous_format)
 
 
 def flash_attention(q, k, v, causal: bool = True) -> torch.Tensor:
