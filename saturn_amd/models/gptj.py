@@ -36,6 +36,8 @@ from saturn_amd.ops.functional import (
     FusedEmbedding,
     gptj_mlp,
     mlp_fused_supported,
+    gptj_branches,
+    gptj_branches_supported,
 )
 
 
@@ -142,8 +144,60 @@ class GPTJBlock(nn.Module):
         # reference resid_pdrop (GPTJ.py:95-96); 0.0 = exact passthrough
         self.drop = FusedDropout(cfg.resid_pdrop)
 
+    @staticmethod
+    def _hooked(m) -> bool:
+        return bool(
+            m._forward_hooks
+            or m._forward_pre_hooks
+            or m._backward_hooks
+            or m._backward_pre_hooks
+        )
+
+    def _use_fused(self, h) -> bool:
+        if (os.environ.get("SAMD_MLP_FUSED", "1") == "0"
+                or os.environ.get("SAMD_BLOCK_FUSED", "1") == "0"):
+            return False
+        attn, mlp = self.attn, self.mlp
+        if type(attn) is not GPTJAttention or type(mlp) is not GPTJMLP:
+            return False
+        if not (h.is_cuda and h.dtype == torch.bfloat16 and h.dim() == 3):
+            return False
+        if self.drop.p != 0.0:
+            return False
+        from saturn_amd.parallel.sequence import sp_world
+
+        if sp_world() != 1:
+            return False
+        if any(self._hooked(m) for b in (attn, mlp, self.drop) for m in b.modules()):
+            return False
+        projs = (attn.q_proj, attn.k_proj, attn.v_proj, attn.out_proj)
+        fi, fo = mlp.fc_in, mlp.fc_out
+        if not all(GPTJMLP._plain_linear(m) for m in (*projs, fi, fo)):
+            return False
+        E = h.shape[-1]
+        if any(m.bias is not None or m.weight.shape != (E, E)
+               or m.weight.dtype != torch.bfloat16 or not m.weight.is_cuda
+               for m in projs):
+            return False
+        return mlp_fused_supported(
+            h, fi.weight, fi.bias, fo.weight, fo.bias
+        ) and gptj_branches_supported(
+            h, attn.n_head, attn.rotary_dim, attn._rope_f32[0].shape[0]
+        )
+
     def forward(self, x):
         h = self.ln_1(x)
+        if self._use_fused(h):
+            # same forward calls; one backward node for both branches
+            # (gptj_block_bwd.hip) shares g^T and h^T between them
+            attn, mlp = self.attn, self.mlp
+            cos, sin = attn._rope(h.device)
+            a, m = gptj_branches(
+                h, attn.q_proj.weight, attn.k_proj.weight, attn.v_proj.weight,
+                attn.out_proj.weight, mlp.fc_in.weight, mlp.fc_in.bias,
+                mlp.fc_out.weight, mlp.fc_out.bias, cos, sin, attn.n_head,
+            )
+            return fused_add3(x, a, m)
         return fused_add3(x, self.drop(self.attn(h)), self.drop(self.mlp(h)))
 
 

@@ -56,6 +56,16 @@ std::vector<at::Tensor> transpose_colsum(at::Tensor x, bool want_sum);
 std::vector<at::Tensor> mlp_bwd(at::Tensor g, at::Tensor h, at::Tensor pre,
                                 at::Tensor W_in, at::Tensor W_out,
                                 bool use_tn_in, bool use_tn_out);
+void transpose_into(at::Tensor x, at::Tensor dst);
+at::Tensor rope_bwd_t(at::Tensor dy, at::Tensor cos_t, at::Tensor sin_t,
+                      int64_t t_len, int64_t t_off, int64_t dim,
+                      at::Tensor dxT);
+std::vector<at::Tensor> gptj_branches_bwd(
+    at::Tensor g_a, at::Tensor g_m, at::Tensor h, at::Tensor pre, at::Tensor q,
+    at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse, at::Tensor Wq,
+    at::Tensor Wk, at::Tensor Wv, at::Tensor Wo, at::Tensor W_in,
+    at::Tensor W_out, at::Tensor cos_t, at::Tensor sin_t, int64_t t_off,
+    bool tn_in, bool tn_out, bool tn_qkv, bool tn_o, bool dh_accum);
 }  // namespace samd
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -108,4 +118,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "bf16 transpose with optional fp32 column sums");
   m.def("mlp_bwd", &samd::mlp_bwd,
         "GPT-J MLP backward with TN-layout weight gradients");
+  m.def("transpose_into", &samd::transpose_into,
+        "bf16 transpose stored into a caller-given [N, M] view",
+        py::arg("x"), py::arg("dst"));
+  m.def("rope_bwd_t", &samd::rope_bwd_t,
+        "interleaved RoPE backward that also stores dx^T into a [E, M] view",
+        py::arg("dy"), py::arg("cos"), py::arg("sin"), py::arg("t_len"),
+        py::arg("t_off"), py::arg("dim"), py::arg("dxT"));
+  m.def("gptj_branches_bwd", &samd::gptj_branches_bwd,
+        "GPT-J attention + MLP branch backward with shared transposes");
 }

@@ -33,63 +33,11 @@
 
 #include "common.h"
 #include "gelu_math.h"
+#include "tile_image.h"
 
 namespace samd {
 
 namespace {
-
-constexpr int MB_TILE = 64;
-constexpr int MB_ROW_ITERS = 4;
-constexpr int MB_BLOCK = 256;
-
-// the same 16-bit type gelu_kernel is instantiated with, so toF/fromF
-// round identically
-typedef c10::BFloat16 bf16_t;
-
-// dword index of (image row c, source-row pair rp) in the swizzled image
-__device__ __forceinline__ int img_dword(int c, int rp) {
-  return c * 32 + (((rp >> 2) ^ (c >> 3)) << 2) + (rp & 3);
-}
-// 16-B slot index of (image row c, source rows 8mv..8mv+7)
-__device__ __forceinline__ int img_slot(int c, int mv) {
-  return c * 8 + (mv ^ (c >> 3));
-}
-
-__device__ __forceinline__ float sum8_bf16(const uint4 v) {
-  float s = us2f((unsigned short)(v.x & 0xffffu));
-  s += us2f((unsigned short)(v.x >> 16));
-  s += us2f((unsigned short)(v.y & 0xffffu));
-  s += us2f((unsigned short)(v.y >> 16));
-  s += us2f((unsigned short)(v.z & 0xffffu));
-  s += us2f((unsigned short)(v.z >> 16));
-  s += us2f((unsigned short)(v.w & 0xffffu));
-  s += us2f((unsigned short)(v.w >> 16));
-  return s;
-}
-
-// Sum the 8 lanes that share an image row, gather the block's 64 column
-// sums in LDS and store them as 16 float4.
-__device__ __forceinline__ void store_colsums(float acc0, float acc1,
-                                              float4* lds_sum,
-                                              float* __restrict__ partial,
-                                              long col0, long ncols) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int off = 1; off < 8; off <<= 1) {
-    acc0 += __shfl_xor(acc0, off, 64);
-    acc1 += __shfl_xor(acc1, off, 64);
-  }
-  float* s = reinterpret_cast<float*>(lds_sum);
-  if ((tid & 7) == 0) {
-    s[tid >> 3] = acc0;
-    s[(tid >> 3) + 32] = acc1;
-  }
-  __syncthreads();
-  if (tid < MB_TILE / 4 && col0 + tid * 4 < ncols) {
-    *reinterpret_cast<float4*>(partial + (long)blockIdx.y * ncols + col0 +
-                               tid * 4) = lds_sum[tid];
-  }
-}
 
 // TN_IN: store d_pre^T.  TN_OUT: store gelu(pre)^T into `act`, else store
 // gelu(pre) row-major there (the NT weight gradient reads it that way).
@@ -247,30 +195,6 @@ transpose_colsum_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ xT,
   if (SUM) store_colsums(acc0, acc1, lds_sum, partial, col0, N);
 }
 
-void check_operand(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, ": expected a GPU tensor");
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, ": expected bf16");
-  TORCH_CHECK(t.dim() == 2 && t.is_contiguous(), name,
-              ": expected a contiguous 2-D tensor");
-  TORCH_CHECK(t.size(0) > 0 && t.size(0) % 8 == 0 && t.size(1) > 0 &&
-                  t.size(1) % 8 == 0,
-              name, ": both sizes must be positive multiples of 8, got ",
-              t.sizes());
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
-              ": data must be 16-byte aligned");
-}
-
-dim3 tile_grid(long M, long N) {
-  const long gx = (N + MB_TILE - 1) / MB_TILE;
-  const long gy = (M + MB_TILE * MB_ROW_ITERS - 1) / (MB_TILE * MB_ROW_ITERS);
-  TORCH_CHECK(gy <= 65535, "mlp_bwd: too many rows for one launch");
-  return dim3((unsigned)gx, (unsigned)gy);
-}
-
-bf16_t* bptr(const at::Tensor& t) {
-  return reinterpret_cast<bf16_t*>(t.data_ptr());
-}
-
 }  // namespace
 
 // Returns (d_pre[M,F], d_preT[F,M], actT[F,M], db[F] fp32).  With
@@ -304,16 +228,27 @@ std::vector<at::Tensor> mlp_act_bwd(at::Tensor d_act, at::Tensor pre,
   return {d_pre, d_preT, act, at::sum(partial, {0})};
 }
 
-namespace {
-
-// want_store=false returns an empty xT; want_sum=false an empty colsum.
-std::vector<at::Tensor> transpose_colsum_impl(const at::Tensor& x,
-                                              bool want_sum, bool want_store) {
+// Declared in tile_image.h.  want_store=false returns an empty xT;
+// want_sum=false an empty colsum; `dst` takes the transpose instead of a
+// fresh tensor.
+std::vector<at::Tensor> transpose_colsum_impl(
+    const at::Tensor& x, bool want_sum, bool want_store,
+    const c10::optional<at::Tensor>& dst) {
   check_operand(x, "transpose_colsum x");
   TORCH_CHECK(want_sum || want_store, "transpose_colsum: nothing to do");
   const long M = x.size(0), N = x.size(1);
-  auto xT = want_store ? at::empty({N, M}, x.options())
-                       : at::empty({0}, x.options());
+  at::Tensor xT;
+  if (want_store && dst.has_value()) {
+    xT = *dst;
+    check_operand(xT, "transpose_colsum dst");
+    TORCH_CHECK(xT.size(0) == N && xT.size(1) == M &&
+                    xT.device() == x.device(),
+                "transpose_colsum: dst must be [", N, ", ", M, "], got ",
+                xT.sizes());
+  } else {
+    xT = want_store ? at::empty({N, M}, x.options())
+                    : at::empty({0}, x.options());
+  }
   const dim3 grid = tile_grid(M, N);
   const auto fopt = x.options().dtype(at::kFloat);
   auto partial = want_sum ? at::empty({(long)grid.y, N}, fopt)
@@ -332,11 +267,15 @@ std::vector<at::Tensor> transpose_colsum_impl(const at::Tensor& x,
   return {xT, want_sum ? at::sum(partial, {0}) : partial};
 }
 
-}  // namespace
-
 // Returns (xT[N,M], colsum[N] fp32); colsum is empty without want_sum.
 std::vector<at::Tensor> transpose_colsum(at::Tensor x, bool want_sum) {
   return transpose_colsum_impl(x, want_sum, true);
+}
+
+// x^T into `dst`, a contiguous [N, M] view such as a row slice of a larger
+// [*, M] buffer.
+void transpose_into(at::Tensor x, at::Tensor dst) {
+  transpose_colsum_impl(x, false, true, dst);
 }
 
 // Whole MLP backward for out = fc_out(gelu(fc_in(h))):

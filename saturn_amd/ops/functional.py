@@ -406,6 +406,129 @@ def gptj_mlp(h, w_in, b_in, w_out, b_out):
     return _GPTJMlpFn.apply(h, w_in, b_in, w_out, b_out)
 
 
+# ---------------------------------------------------------------------------
+# GPT-J parallel block: attention and MLP branches as one autograd node
+# (gptj_block_bwd.hip).  Both branches get the same incoming gradient g and
+# read the same h, so one node shares g^T and h^T between them and runs the
+# attention weight gradients as TN GEMMs too; optionally dh accumulates in
+# the GEMMs (addmm) instead of through three elementwise adds.
+# ---------------------------------------------------------------------------
+# Per-site defaults from profiles/r04_attn_wgrad_probe.txt; SAMD_ATTN_TN_QKV /
+# SAMD_ATTN_TN_OUT / SAMD_DH_ACCUM = 0|1 override them for A/B runs.
+_BLOCK_SITE_DEFAULT = {
+    "SAMD_ATTN_TN_QKV": True,
+    "SAMD_ATTN_TN_OUT": True,
+    "SAMD_DH_ACCUM": False,  # saving within the spread of its GEMM arms
+}
+
+
+def _block_site(name: str) -> bool:
+    v = os.environ.get(name)
+    return _BLOCK_SITE_DEFAULT[name] if v is None else v != "0"
+
+
+def _same_tensor(a, b) -> bool:
+    return (
+        a.data_ptr() == b.data_ptr()
+        and a.shape == b.shape
+        and a.stride() == b.stride()
+    )
+
+
+class _GPTJBranchesFn(torch.autograd.Function):
+    """h -> (out_proj(attn(rope(q_proj h), rope(k_proj h), v_proj h)),
+    fc_out(gelu(fc_in h))).  The forward makes the unfused path's calls in
+    its order, so both outputs carry the same bits; it saves h, pre, the
+    rotated q and k, v, o and lse, as the separate nodes do."""
+
+    @staticmethod
+    def forward(ctx, h, wq, wk, wv, wo, w_in, b_in, w_out, b_out, cos, sin,
+                n_head, t_off):
+        ext = require_ext()
+        B, T, E = h.shape
+        D = E // n_head
+        q = F.linear(h, wq).view(B, T, n_head, D)
+        k = F.linear(h, wk).view(B, T, n_head, D)
+        v = F.linear(h, wv).view(B, T, n_head, D)
+        qr = torch.empty_like(q)
+        ext.rope_apply(qr, q, cos, sin, T, t_off, False, False)
+        kr = torch.empty_like(k)
+        ext.rope_apply(kr, k, cos, sin, T, t_off, False, False)
+        del q, k
+        qr, kr, v = qr.transpose(1, 2), kr.transpose(1, 2), v.transpose(1, 2)
+        o, lse = ext.attn_fwd(qr, kr, v, True, T)
+        attn_out = F.linear(o.transpose(1, 2).reshape(B, T, E), wo)
+        pre = F.linear(h, w_in, b_in).contiguous()
+        mlp_out = F.linear(ext.gelu_fwd(pre), w_out, b_out)
+        ctx.save_for_backward(h, pre, qr, kr, v, o, lse, wq, wk, wv, wo,
+                              w_in, w_out, cos, sin)
+        ctx.t_off = t_off
+        return attn_out, mlp_out
+
+    @staticmethod
+    def backward(ctx, g_a, g_m):
+        ext = require_ext()
+        (h, pre, qr, kr, v, o, lse, wq, wk, wv, wo, w_in, w_out, cos,
+         sin) = ctx.saved_tensors
+        E = h.shape[-1]
+        if g_a is None:
+            g_a = torch.zeros_like(h)
+        if g_m is None:
+            g_m = torch.zeros_like(h)
+        if _same_tensor(g_a, g_m):
+            # add3's backward hands one g to both branches: share g^T
+            g_a = g_m = g_m.contiguous().view(-1, E)
+        else:
+            g_a = g_a.contiguous().view(-1, E)
+            g_m = g_m.contiguous().view(-1, E)
+        dh, dwq, dwk, dwv, dwo, dw_in, db_in, dw_out, db_out = (
+            ext.gptj_branches_bwd(
+                g_a, g_m,
+                h.contiguous().view(-1, E),
+                pre.view(-1, pre.shape[-1]),
+                qr, kr, v, o, lse,
+                wq.contiguous(), wk.contiguous(), wv.contiguous(),
+                wo.contiguous(), w_in.contiguous(), w_out.contiguous(),
+                cos, sin, ctx.t_off,
+                _mlp_tn("in"), _mlp_tn("out"),
+                _block_site("SAMD_ATTN_TN_QKV"),
+                _block_site("SAMD_ATTN_TN_OUT"),
+                _block_site("SAMD_DH_ACCUM"),
+            )
+        )
+        return (dh.view(h.shape), dwq, dwk, dwv, dwo, dw_in, db_in, dw_out,
+                db_out, None, None, None, None)
+
+
+def gptj_branches_supported(h, n_head, rotary_dim, table_len) -> bool:
+    """Shapes ``ext.gptj_branches_bwd`` accepts beyond those of
+    ``mlp_fused_supported``: [B, T, E] with T a multiple of the attention
+    kernels' 64-row tile and within the RoPE table, a head dim the MFMA
+    kernels have, and a rotary width the vector RoPE kernel takes."""
+    if h.dim() != 3 or n_head <= 0:
+        return False
+    B, T, E = h.shape
+    if E % n_head:
+        return False
+    D = E // n_head
+    return (
+        T % 64 == 0
+        and T <= table_len
+        and D in (64, 128, 256)
+        and rotary_dim > 0
+        and rotary_dim % 8 == 0
+        and rotary_dim <= D
+    )
+
+
+def gptj_branches(h, wq, wk, wv, wo, w_in, b_in, w_out, b_out, cos, sin,
+                  n_head):
+    """Both branches of a GPT-J block through one backward node; callers
+    check ``mlp_fused_supported`` and ``gptj_branches_supported`` first."""
+    return _GPTJBranchesFn.apply(h, wq, wk, wv, wo, w_in, b_in, w_out, b_out,
+                                 cos.contiguous(), sin.contiguous(), n_head, 0)
+
+
 class _SwigluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gate, up):

@@ -32,6 +32,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "dropout.hip"),
         os.path.join(CSRC, "moe.hip"),
         os.path.join(CSRC, "mlp_bwd.hip"),
+        os.path.join(CSRC, "gptj_block_bwd.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
