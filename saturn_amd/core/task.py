@@ -17,6 +17,7 @@ Capability parity with the reference's ``saturn/core/representations/Task.py``
 
 from __future__ import annotations
 
+import math
 import os
 import random
 import string
@@ -40,6 +41,10 @@ class HParams:
         epochs).
     optimizer_cls : optimizer class; instantiated by the executor.  When None
         the executor defaults to the framework's fused SGD.
+    max_grad_norm : clip the gradient of the whole model to this global L2
+        norm before every update (None: no clipping).  Every executor
+        applies it so that the norm is the one a dense single-process run
+        reports; a step whose norm is not finite is skipped.
     kwargs : forwarded to the user's ``get_model`` factory.
     """
 
@@ -49,6 +54,7 @@ class HParams:
         epochs: Optional[int] = None,
         batch_count: Optional[int] = None,
         optimizer_cls: Optional[type] = None,
+        max_grad_norm: Optional[float] = None,
         **kwargs: Any,
     ) -> None:
         if (batch_count is None) == (epochs is None):
@@ -59,6 +65,14 @@ class HParams:
         self.epochs = epochs
         self.batch_count = batch_count
         self.optimizer_cls = optimizer_cls
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not math.isfinite(max_grad_norm) or max_grad_norm <= 0.0:
+                raise ValueError(
+                    "`max_grad_norm` must be a finite positive number, got "
+                    f"{max_grad_norm!r}."
+                )
+        self.max_grad_norm = max_grad_norm
         self.kwargs = kwargs
 
     def as_dict(self) -> Dict[str, Any]:
@@ -66,6 +80,7 @@ class HParams:
             "lr": self.lr,
             "epochs": self.epochs,
             "batch_count": self.batch_count,
+            "max_grad_norm": self.max_grad_norm,
         }
 
     def __repr__(self) -> str:
@@ -74,6 +89,8 @@ class HParams:
             if self.epochs is not None
             else f"batch_count={self.batch_count}"
         )
+        if self.max_grad_norm is not None:
+            tail += f", max_grad_norm={self.max_grad_norm}"
         return f"HParams(lr={self.lr}, {tail})"
 
 

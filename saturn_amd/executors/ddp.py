@@ -53,18 +53,69 @@ def build_model_on(task, device, dtype):
     return model.to(device=device, dtype=dtype)
 
 
-def _make_optimizer(task, model):
-    """Task-specified optimizer, defaulting to the framework's fused SGD on
-    GPU / torch SGD on CPU."""
-    import torch
+def _make_optimizer(task, model, norm_reduce=None, replicated=()):
+    """Task-specified optimizer, defaulting to the framework's fused SGD
+    (HIP kernel on GPU, torch fallback on CPU).
 
+    With ``hparams.max_grad_norm`` set, the optimizer clips the global
+    gradient norm at every ``step()``: ``FusedSGD`` does it inside its
+    kernel; a user-given ``optimizer_cls`` gets a step pre-hook that calls
+    the shared ``GradClipper`` (``saturn_amd.ops.clip``), so every
+    executor's ``optimizer.step()`` stays the one call it was.
+    ``norm_reduce`` turns a rank's squared sum over its shards into the whole
+    model's; ``replicated`` names the parameters every rank holds in full
+    (see ``make_norm_reduce``).  Either way ``grad_clip_stats(optimizer)``
+    reads the result."""
     params = list(model.parameters())
     cls = task.hparams.optimizer_cls
+    max_norm = getattr(task.hparams, "max_grad_norm", None)
     if cls is None:
         from saturn_amd.ops.optim import FusedSGD
 
-        return FusedSGD(params, lr=task.hparams.lr)
-    return cls(params, lr=task.hparams.lr)
+        if max_norm is None:
+            return FusedSGD(params, lr=task.hparams.lr)
+        opt = FusedSGD(params, lr=task.hparams.lr, max_grad_norm=max_norm)
+        if norm_reduce is not None:
+            opt.set_norm_reduce(norm_reduce)
+            opt.set_replicated(replicated)
+        return opt
+    opt = cls(params, lr=task.hparams.lr)
+    if max_norm is not None:
+        from saturn_amd.ops.clip import GradClipper
+
+        clipper = GradClipper(max_norm, norm_reduce, replicated)
+        opt._saturn_clipper = clipper
+
+        def clip_before_step(optimizer, args, kwargs):
+            clipper.clip_(params)
+
+        opt.register_step_pre_hook(clip_before_step)
+    return opt
+
+
+def make_norm_reduce(group=None):
+    """``norm_reduce`` for a technique whose ranks hold different shards of
+    the gradient: all-reduce (sum) of the one-element squared sum."""
+
+    def reduce(sq):
+        import torch.distributed as dist
+
+        if dist.is_available() and dist.is_initialized() \
+                and dist.get_world_size(group) > 1:
+            dist.all_reduce(sq, op=dist.ReduceOp.SUM, group=group)
+        return sq
+
+    return reduce
+
+
+def grad_clip_stats(optimizer):
+    """(last global gradient norm, skipped steps) as device tensors, or None
+    when the optimizer does not clip (or has not stepped yet)."""
+    src = getattr(optimizer, "_saturn_clipper", None) or optimizer
+    norm = getattr(src, "last_grad_norm", None)
+    if norm is None:
+        return None
+    return norm, src.skipped_steps
 
 
 def _ddp_worker(
@@ -175,9 +226,16 @@ def _ddp_worker(
             if rank == 0:
                 import logging
 
+                stats = grad_clip_stats(optimizer)
+                clip_note = (
+                    ""
+                    if stats is None
+                    else ", grad norm %.4g, %d steps skipped"
+                    % (float(stats[0]), int(stats[1]))
+                )
                 logging.getLogger(__name__).info(
-                    "task %s: %d batches done, loss %.4f",
-                    task.name, batch_count, float(last_loss[0]),
+                    "task %s: %d batches done, loss %.4f%s",
+                    task.name, batch_count, float(last_loss[0]), clip_note,
                 )
                 task.save_checkpoint(model, optimizer)
             import torch.distributed as dist

@@ -33,7 +33,7 @@ def _ep_worker(rank: int, world: int, task, tid: int, batch_count: int,
     import torch
     import torch.distributed as dist
 
-    from saturn_amd.executors.ddp import _make_optimizer
+    from saturn_amd.executors.ddp import _make_optimizer, make_norm_reduce
     from saturn_amd.parallel.ddp import BucketedDDP
     from saturn_amd.parallel.expert import (
         ep_expert_parameters,
@@ -57,7 +57,19 @@ def _ep_worker(rank: int, world: int, task, tid: int, batch_count: int,
         # BucketedDDP broadcasts + all-reduces only the shared params;
         # expert shards stay rank-local by construction
         ddp = BucketedDDP(model, exclude=experts)
-        optimizer = _make_optimizer(task, model)
+        if task.hparams.max_grad_norm is None:
+            optimizer = _make_optimizer(task, model)
+        else:
+            # expert shards (after ep_scale_expert_grads) are summed over
+            # the gang; everything else is replicated and counted once
+            expert_ids = {id(p) for p in experts}
+            optimizer = _make_optimizer(
+                task, model,
+                norm_reduce=make_norm_reduce(),
+                replicated=[
+                    p for p in model.parameters() if id(p) not in expert_ids
+                ],
+            )
 
         import os as _os
 

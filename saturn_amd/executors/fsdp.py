@@ -35,7 +35,7 @@ def _fsdp_worker(
 ):
     import torch
 
-    from saturn_amd.executors.ddp import _make_optimizer
+    from saturn_amd.executors.ddp import _make_optimizer, make_norm_reduce
     from saturn_amd.parallel.zero3 import Zero3Model
 
     params = params or {}
@@ -65,7 +65,14 @@ def _fsdp_worker(
                 self.ps = nn.ParameterList(shards)
 
         holder = _ShardHolder(z3.sharded_parameters())
-        optimizer = _make_optimizer(task, holder)
+        if task.hparams.max_grad_norm is None:
+            optimizer = _make_optimizer(task, holder)
+        else:
+            # every parameter is a shard: the global norm is the all-reduced
+            # squared sum
+            optimizer = _make_optimizer(
+                task, holder, norm_reduce=make_norm_reduce()
+            )
 
         # Sharded optimizer-state resume (the reference loses optimizer
         # moments at every interval; full-state ckpts carry

@@ -27,9 +27,10 @@ def _tp_worker(rank: int, world: int, task, tid: int, batch_count: int,
     import torch
     import torch.distributed as dist
 
-    from saturn_amd.executors.ddp import _make_optimizer
+    from saturn_amd.executors.ddp import _make_optimizer, make_norm_reduce
     from saturn_amd.parallel.tensor import (
         tp_full_state_dict,
+        tp_replicated_parameters,
         tp_resync_replicated,
         tp_shard_model,
     )
@@ -49,7 +50,15 @@ def _tp_worker(rank: int, world: int, task, tid: int, batch_count: int,
                 for p in model.parameters():
                     dist.broadcast(p.data, src=0)
         model = tp_shard_model(model)
-        optimizer = _make_optimizer(task, model)
+        if task.hparams.max_grad_norm is None:
+            optimizer = _make_optimizer(task, model)
+        else:
+            # global = allreduce(sq(shards)) + sq(replicated)
+            optimizer = _make_optimizer(
+                task, model,
+                norm_reduce=make_norm_reduce(),
+                replicated=list(tp_replicated_parameters(model)),
+            )
 
         # Per-rank optimizer shard resume (mirrors FSDPExecutor: the
         # reference loses moments at every interval; TP shards

@@ -56,7 +56,7 @@ def _run_spilled(task, batch_count: int, params: Optional[Dict[str, Any]],
                  trial: bool):
     import torch
 
-    from saturn_amd.executors.ddp import _make_optimizer
+    from saturn_amd.executors.ddp import _make_optimizer, make_norm_reduce
     from saturn_amd.parallel.zero3 import Zero3Model
 
     params = params or {}
@@ -87,7 +87,14 @@ def _run_spilled(task, batch_count: int, params: Optional[Dict[str, Any]],
             super().__init__()
             self.ps = nn.ParameterList(shards)
 
-    optimizer = _make_optimizer(task, _Holder(z3.sharded_parameters()))
+    if task.hparams.max_grad_norm is None:
+        optimizer = _make_optimizer(task, _Holder(z3.sharded_parameters()))
+    else:
+        # every parameter is a shard of the gang's (here: one rank's) model
+        optimizer = _make_optimizer(
+            task, _Holder(z3.sharded_parameters()),
+            norm_reduce=make_norm_reduce(),
+        )
     it = task.get_iterator() if not trial else task.get_fresh_iterator()
 
     def next_batch():

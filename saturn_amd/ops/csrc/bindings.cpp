@@ -6,12 +6,18 @@
 namespace samd {
 void fused_sgd(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                std::vector<at::Tensor> moms, std::vector<at::Tensor> masters,
-               double lr, double momentum, double weight_decay);
+               double lr, double momentum, double weight_decay,
+               c10::optional<at::Tensor> grad_scale);
 void fused_adam(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                 std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
                 std::vector<at::Tensor> masters, double lr, double beta1,
                 double beta2, double eps, double weight_decay, double bc1,
-                double bc2);
+                double bc2, c10::optional<at::Tensor> grad_scale);
+at::Tensor grad_sqsum(std::vector<at::Tensor> tensors, at::Tensor partials);
+std::vector<std::pair<int64_t, int64_t>> grad_sqsum_plan(
+    std::vector<int64_t> numels);
+int64_t grad_sqsum_slots(int64_t n_tensors);
+void clip_coef(at::Tensor sq, double max_norm, at::Tensor out);
 std::vector<at::Tensor> norm_fwd(at::Tensor x, at::Tensor w,
                                  c10::optional<at::Tensor> b, double eps,
                                  bool rms);
@@ -70,8 +76,27 @@ std::vector<at::Tensor> gptj_branches_bwd(
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "saturn_amd hand-written CDNA4 (gfx950) kernels";
-  m.def("fused_sgd", &samd::fused_sgd, "fused multi-tensor SGD");
-  m.def("fused_adam", &samd::fused_adam, "fused multi-tensor AdamW");
+  m.def("fused_sgd", &samd::fused_sgd, "fused multi-tensor SGD",
+        py::arg("params"), py::arg("grads"), py::arg("moms"),
+        py::arg("masters"), py::arg("lr"), py::arg("momentum"),
+        py::arg("weight_decay"), py::arg("grad_scale") = py::none());
+  m.def("fused_adam", &samd::fused_adam, "fused multi-tensor AdamW",
+        py::arg("params"), py::arg("grads"), py::arg("ms"), py::arg("vs"),
+        py::arg("masters"), py::arg("lr"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        py::arg("bc1"), py::arg("bc2"), py::arg("grad_scale") = py::none());
+  m.def("grad_sqsum", &samd::grad_sqsum,
+        "fp32 sum of squares over a tensor list (no atomics, reproducible)",
+        py::arg("tensors"), py::arg("partials"));
+  m.def("grad_sqsum_plan", &samd::grad_sqsum_plan,
+        "(blocks, threads) of each launch grad_sqsum makes for these sizes",
+        py::arg("numels"));
+  m.def("grad_sqsum_slots", &samd::grad_sqsum_slots,
+        "partials slots a list of n tensors can need (launches x grid cap)",
+        py::arg("n_tensors"));
+  m.def("clip_coef", &samd::clip_coef,
+        "out = {norm, coef, skipped_total} from a squared gradient sum",
+        py::arg("sq"), py::arg("max_norm"), py::arg("out"));
   m.def("norm_fwd", &samd::norm_fwd, "LayerNorm/RMSNorm forward");
   m.def("norm_bwd", &samd::norm_bwd, "LayerNorm/RMSNorm backward");
   m.def("ce_fwd", &samd::ce_fwd, "fused cross-entropy forward");

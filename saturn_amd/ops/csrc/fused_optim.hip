@@ -33,14 +33,33 @@ struct SgdArgs {
   long numel[MAX_T];
   int n_tensors;
   float lr, momentum, weight_decay;
+  const float* scale;   // {norm, coef, ...} from clip_coef (HAS_S only)
 };
 
-template <typename T, bool HAS_M, bool HAS_W>
+// Gradient scale from clip_coef's output: false when the step is skipped
+// (non-finite norm).  The multiply by coef is kept out of fp contraction:
+// g * coef is rounded on its own, as clip_grad_norm_ followed by the
+// optimizer rounds it, and coef == 1 leaves every later operation the one
+// the unscaled kernel does.
+__device__ __forceinline__ bool load_grad_scale(const float* scale,
+                                                float& coef) {
+  const float norm = scale[0];
+  coef = scale[1];
+  return (__float_as_uint(norm) & 0x7f800000u) != 0x7f800000u;
+}
+__device__ __forceinline__ float scale_grad(float g, float coef) {
+#pragma clang fp contract(off)
+  return g * coef;
+}
+
+template <typename T, bool HAS_M, bool HAS_W, bool HAS_S>
 __device__ __forceinline__ void sgd_elem(T* p, const T* g, float* m, float* w,
-                                         long j, const SgdArgs& a) {
+                                         long j, const SgdArgs& a,
+                                         float coef) {
   // HAS_W: the fp32 master is the source of truth; p gets the rounded copy.
   float pv = HAS_W ? w[j] : toF<T>(p[j]);
   float gv = toF<T>(g[j]);
+  if (HAS_S) gv = scale_grad(gv, coef);
   if (a.weight_decay != 0.f) gv += a.weight_decay * pv;
   if (HAS_M) {
     float mv = m[j] * a.momentum + gv;
@@ -52,8 +71,12 @@ __device__ __forceinline__ void sgd_elem(T* p, const T* g, float* m, float* w,
   p[j] = fromF<T>(nv);
 }
 
-template <typename T, bool HAS_M, bool HAS_W>
+template <typename T, bool HAS_M, bool HAS_W, bool HAS_S>
 __global__ void fused_sgd_kernel(SgdArgs a) {
+  float coef = 1.f;
+  if constexpr (HAS_S) {
+    if (!load_grad_scale(a.scale, coef)) return;
+  }
   const long total = a.cum[a.n_tensors];  // total groups
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total;
@@ -90,6 +113,7 @@ __global__ void fused_sgd_kernel(SgdArgs a) {
           ge.x = (unsigned short)gv[e];
           float pf = HAS_W ? (e < 4 ? w0[e] : w1[e - 4]) : toF<T>(pe);
           float gf = toF<T>(ge);
+          if (HAS_S) gf = scale_grad(gf, coef);
           if (a.weight_decay != 0.f) gf += a.weight_decay * pf;
           if (HAS_M) {
             float mv = (e < 4 ? m0[e] : m1[e - 4]) * a.momentum + gf;
@@ -114,12 +138,12 @@ __global__ void fused_sgd_kernel(SgdArgs a) {
         }
       } else {
         for (long j = base; j < n; ++j)
-          sgd_elem<T, HAS_M, HAS_W>(p, g, m, w, j, a);
+          sgd_elem<T, HAS_M, HAS_W, HAS_S>(p, g, m, w, j, a, coef);
       }
     } else {
       const long end = (base + GRP <= n) ? base + GRP : n;
       for (long j = base; j < end; ++j)
-        sgd_elem<T, HAS_M, HAS_W>(p, g, m, w, j, a);
+        sgd_elem<T, HAS_M, HAS_W, HAS_S>(p, g, m, w, j, a, coef);
     }
   }
 }
@@ -134,13 +158,16 @@ struct AdamArgs {
   long numel[MAX_T];
   int n_tensors;
   float lr, beta1, beta2, eps, weight_decay, bc1, bc2;
+  const float* scale;  // {norm, coef, ...} from clip_coef (HAS_S only)
 };
 
-template <typename T, bool HAS_W>
+template <typename T, bool HAS_W, bool HAS_S>
 __device__ __forceinline__ void adam_elem(T* p, const T* g, float* m, float* v,
                                           float* w, long j, const AdamArgs& a,
-                                          float inv_bc1, float inv_bc2) {
+                                          float inv_bc1, float inv_bc2,
+                                          float coef) {
   float gv = toF<T>(g[j]);
+  if (HAS_S) gv = scale_grad(gv, coef);
   float mv = a.beta1 * m[j] + (1.f - a.beta1) * gv;
   float vv = a.beta2 * v[j] + (1.f - a.beta2) * gv * gv;
   m[j] = mv;
@@ -154,8 +181,12 @@ __device__ __forceinline__ void adam_elem(T* p, const T* g, float* m, float* v,
   p[j] = fromF<T>(nv);
 }
 
-template <typename T, bool HAS_W>
+template <typename T, bool HAS_W, bool HAS_S>
 __global__ void fused_adam_kernel(AdamArgs a) {
+  float coef = 1.f;
+  if constexpr (HAS_S) {
+    if (!load_grad_scale(a.scale, coef)) return;
+  }
   const long total = a.cum[a.n_tensors];
   const long stride = (long)gridDim.x * blockDim.x;
   const float inv_bc1 = 1.f / a.bc1;
@@ -193,6 +224,7 @@ __global__ void fused_adam_kernel(AdamArgs a) {
           T ge;
           ge.x = (unsigned short)gv[e];
           float gf = toF<T>(ge);
+          if (HAS_S) gf = scale_grad(gf, coef);
           float mv = a.beta1 * (e < 4 ? m0[e] : m1[e - 4]) + (1.f - a.beta1) * gf;
           float vv = a.beta2 * (e < 4 ? v0[e] : v1[e - 4]) + (1.f - a.beta2) * gf * gf;
           if (e < 4) { m0[e] = mv; v0[e] = vv; } else { m1[e-4] = mv; v1[e-4] = vv; }
@@ -220,12 +252,12 @@ __global__ void fused_adam_kernel(AdamArgs a) {
         }
       } else {
         for (long j = base; j < n; ++j)
-          adam_elem<T, HAS_W>(p, g, m, v, w, j, a, inv_bc1, inv_bc2);
+          adam_elem<T, HAS_W, HAS_S>(p, g, m, v, w, j, a, inv_bc1, inv_bc2, coef);
       }
     } else {
       const long end = (base + GRP <= n) ? base + GRP : n;
       for (long j = base; j < end; ++j)
-        adam_elem<T, HAS_W>(p, g, m, v, w, j, a, inv_bc1, inv_bc2);
+        adam_elem<T, HAS_W, HAS_S>(p, g, m, v, w, j, a, inv_bc1, inv_bc2, coef);
     }
   }
 }
@@ -240,12 +272,24 @@ static int grid_for(long total, int block) {
 
 static long groups_of(long numel) { return (numel + GRP - 1) / GRP; }
 
+// clip_coef's output tensor, or nullptr when the step is not clipped
+static const float* grad_scale_ptr(const c10::optional<at::Tensor>& gs,
+                                   const at::Tensor& like) {
+  if (!gs.has_value()) return nullptr;
+  TORCH_CHECK(gs->scalar_type() == at::kFloat && gs->numel() >= 2 &&
+                  gs->is_contiguous() && gs->device() == like.device(),
+              "grad_scale must be clip_coef's fp32 output on the parameters' "
+              "device");
+  return gs->data_ptr<float>();
+}
+
 template <typename scalar_t>
 static void sgd_launch(std::vector<at::Tensor>& params,
                        std::vector<at::Tensor>& grads,
                        std::vector<at::Tensor>& moms,
                        std::vector<at::Tensor>& masters, double lr,
-                       double momentum, double weight_decay) {
+                       double momentum, double weight_decay,
+                       const float* scale) {
   auto stream = at::hip::getCurrentHIPStream();
   const bool has_m = !moms.empty();
   const bool has_w = !masters.empty();
@@ -255,6 +299,7 @@ static void sgd_launch(std::vector<at::Tensor>& params,
     a.lr = (float)lr;
     a.momentum = (float)momentum;
     a.weight_decay = (float)weight_decay;
+    a.scale = scale;
     long cum = 0;
     a.cum[0] = 0;
     for (int k = 0; k < a.n_tensors; ++k) {
@@ -268,24 +313,27 @@ static void sgd_launch(std::vector<at::Tensor>& params,
     }
     const int block = 256;
     dim3 grid(grid_for(cum, block));
-    if (has_m && has_w)
-      hipLaunchKernelGGL((fused_sgd_kernel<scalar_t, true, true>), grid,
-                         dim3(block), 0, stream.stream(), a);
-    else if (has_m)
-      hipLaunchKernelGGL((fused_sgd_kernel<scalar_t, true, false>), grid,
-                         dim3(block), 0, stream.stream(), a);
-    else if (has_w)
-      hipLaunchKernelGGL((fused_sgd_kernel<scalar_t, false, true>), grid,
-                         dim3(block), 0, stream.stream(), a);
-    else
-      hipLaunchKernelGGL((fused_sgd_kernel<scalar_t, false, false>), grid,
-                         dim3(block), 0, stream.stream(), a);
+#define SAMD_SGD_LAUNCH(M, W, S)                                          \
+  hipLaunchKernelGGL((fused_sgd_kernel<scalar_t, M, W, S>), grid,         \
+                     dim3(block), 0, stream.stream(), a)
+#define SAMD_SGD_MW(S)                                                    \
+  do {                                                                    \
+    if (has_m && has_w) SAMD_SGD_LAUNCH(true, true, S);                   \
+    else if (has_m) SAMD_SGD_LAUNCH(true, false, S);                      \
+    else if (has_w) SAMD_SGD_LAUNCH(false, true, S);                      \
+    else SAMD_SGD_LAUNCH(false, false, S);                                \
+  } while (0)
+    if (scale != nullptr) SAMD_SGD_MW(true);
+    else SAMD_SGD_MW(false);
+#undef SAMD_SGD_MW
+#undef SAMD_SGD_LAUNCH
   }
 }
 
 void fused_sgd(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                std::vector<at::Tensor> moms, std::vector<at::Tensor> masters,
-               double lr, double momentum, double weight_decay) {
+               double lr, double momentum, double weight_decay,
+               c10::optional<at::Tensor> grad_scale) {
   TORCH_CHECK(!params.empty(), "no params");
   TORCH_CHECK(params.size() == grads.size());
   TORCH_CHECK(moms.empty() || moms.size() == params.size());
@@ -301,18 +349,19 @@ void fused_sgd(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                       masters[i].is_contiguous(),
                   "master weights must be contiguous fp32");
   }
+  const float* scale = grad_scale_ptr(grad_scale, params[0]);
   switch (params[0].scalar_type()) {
     case at::kBFloat16:
       sgd_launch<c10::BFloat16>(params, grads, moms, masters, lr, momentum,
-                                weight_decay);
+                                weight_decay, scale);
       break;
     case at::kFloat:
       sgd_launch<float>(params, grads, moms, masters, lr, momentum,
-                        weight_decay);
+                        weight_decay, scale);
       break;
     case at::kHalf:
       sgd_launch<c10::Half>(params, grads, moms, masters, lr, momentum,
-                            weight_decay);
+                            weight_decay, scale);
       break;
     default:
       TORCH_CHECK(false, "fused_sgd: unsupported dtype");
@@ -326,7 +375,8 @@ static void adam_launch(std::vector<at::Tensor>& params,
                         std::vector<at::Tensor>& vs,
                         std::vector<at::Tensor>& masters, double lr,
                         double beta1, double beta2, double eps,
-                        double weight_decay, double bc1, double bc2) {
+                        double weight_decay, double bc1, double bc2,
+                        const float* scale) {
   auto stream = at::hip::getCurrentHIPStream();
   const bool has_w = !masters.empty();
   for (size_t base = 0; base < params.size(); base += MAX_T) {
@@ -339,6 +389,7 @@ static void adam_launch(std::vector<at::Tensor>& params,
     a.weight_decay = (float)weight_decay;
     a.bc1 = (float)bc1;
     a.bc2 = (float)bc2;
+    a.scale = scale;
     long cum = 0;
     a.cum[0] = 0;
     for (int k = 0; k < a.n_tensors; ++k) {
@@ -353,12 +404,20 @@ static void adam_launch(std::vector<at::Tensor>& params,
     }
     const int block = 256;
     dim3 grid(grid_for(cum, block));
-    if (has_w)
-      hipLaunchKernelGGL((fused_adam_kernel<scalar_t, true>), grid,
+    if (scale != nullptr) {
+      if (has_w)
+        hipLaunchKernelGGL((fused_adam_kernel<scalar_t, true, true>), grid,
+                           dim3(block), 0, stream.stream(), a);
+      else
+        hipLaunchKernelGGL((fused_adam_kernel<scalar_t, false, true>), grid,
+                           dim3(block), 0, stream.stream(), a);
+    } else if (has_w) {
+      hipLaunchKernelGGL((fused_adam_kernel<scalar_t, true, false>), grid,
                          dim3(block), 0, stream.stream(), a);
-    else
-      hipLaunchKernelGGL((fused_adam_kernel<scalar_t, false>), grid,
+    } else {
+      hipLaunchKernelGGL((fused_adam_kernel<scalar_t, false, false>), grid,
                          dim3(block), 0, stream.stream(), a);
+    }
   }
 }
 
@@ -366,7 +425,7 @@ void fused_adam(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                 std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
                 std::vector<at::Tensor> masters, double lr, double beta1,
                 double beta2, double eps, double weight_decay, double bc1,
-                double bc2) {
+                double bc2, c10::optional<at::Tensor> grad_scale) {
   TORCH_CHECK(!params.empty(), "no params");
   TORCH_CHECK(params.size() == grads.size() && params.size() == ms.size() &&
               params.size() == vs.size());
@@ -381,14 +440,15 @@ void fused_adam(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                       masters[i].is_contiguous(),
                   "master weights must be contiguous fp32");
   }
+  const float* scale = grad_scale_ptr(grad_scale, params[0]);
   switch (params[0].scalar_type()) {
     case at::kBFloat16:
       adam_launch<c10::BFloat16>(params, grads, ms, vs, masters, lr, beta1,
-                                 beta2, eps, weight_decay, bc1, bc2);
+                                 beta2, eps, weight_decay, bc1, bc2, scale);
       break;
     case at::kFloat:
       adam_launch<float>(params, grads, ms, vs, masters, lr, beta1, beta2,
-                         eps, weight_decay, bc1, bc2);
+                         eps, weight_decay, bc1, bc2, scale);
       break;
     default:
       TORCH_CHECK(false, "fused_adam: unsupported dtype");

@@ -13,17 +13,27 @@ no-GPU container with the same numerics contract as the kernel:
   rounded bf16/fp16 copy in the same launch, avoiding long-horizon update
   cancellation when ``lr * grad`` drops below bf16 resolution.  The
   reference trains fp32 models (simple-verification.py:59) and never had
-  this problem.
+  this problem;
+- ``max_grad_norm`` clips the gradient of the whole model to that global
+  norm (``saturn_amd.ops.clip``): one read-only reduction leaves
+  ``{norm, coef, skipped_total}`` on the device and the update kernels
+  multiply ``g`` by ``coef`` as they load it, before weight decay and
+  momentum — the order ``clip_grad_norm_`` followed by the optimizer gives.
+  A step whose norm is not finite is skipped on the device: parameters,
+  momentum, moments and masters stay as they are.  Nothing is read on the
+  host, so a clipped step captures into a hipGraph like an unclipped one.
 """
 
 from __future__ import annotations
 
 
-from typing import Iterable, List, Optional
+import math
+from typing import Callable, Iterable, List, Optional
 
 import torch
 
 from saturn_amd.ops import require_ext
+from saturn_amd.ops.clip import GradClipper, check_max_grad_norm
 
 
 def _grouped(params_with_grads: List[torch.nn.Parameter]):
@@ -34,8 +44,83 @@ def _grouped(params_with_grads: List[torch.nn.Parameter]):
     return groups
 
 
-class FusedSGD(torch.optim.Optimizer):
-    """SGD with optional momentum/weight decay, fused on GPU."""
+class _ClipMixin:
+    """``max_grad_norm`` support shared by the fused optimizers."""
+
+    _clipper: Optional[GradClipper] = None
+
+    def _init_clip(self, max_grad_norm: Optional[float]) -> None:
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        self._clipper = (
+            GradClipper(self.max_grad_norm)
+            if self.max_grad_norm is not None
+            else None
+        )
+
+    @property
+    def norm_reduce(self) -> Optional[Callable[[torch.Tensor], torch.Tensor]]:
+        return None if self._clipper is None else self._clipper.norm_reduce
+
+    def set_norm_reduce(
+        self, fn: Optional[Callable[[torch.Tensor], torch.Tensor]]
+    ) -> None:
+        """``fn(sq_local: Tensor[1]) -> Tensor[1]`` turns this rank's squared
+        gradient sum into the whole model's (an all-reduce over the ranks
+        that hold the other shards)."""
+        if self._clipper is None:
+            raise ValueError("set_norm_reduce needs max_grad_norm")
+        self._clipper.norm_reduce = fn
+
+    def set_replicated(self, params: Iterable[torch.Tensor]) -> None:
+        """Name the parameters whose gradients are identical on every rank of
+        the reduction: they are added once, after ``norm_reduce``."""
+        if self._clipper is None:
+            raise ValueError("set_replicated needs max_grad_norm")
+        self._clipper.set_replicated(params)
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        """Global gradient norm of the last step, before clipping: a device
+        tensor, never synchronised here (None before the first step)."""
+        return None if self._clipper is None else self._clipper.last_grad_norm
+
+    @property
+    def skipped_steps(self) -> Optional[torch.Tensor]:
+        """Number of steps skipped for a non-finite norm (device tensor)."""
+        return None if self._clipper is None else self._clipper.skipped_steps
+
+    def _clip_begin(self):
+        """Refresh the coefficient from every gradient this step will use;
+        returns ``scale_for(device) -> Tensor | None`` for the launches."""
+        if self._clipper is None:
+            return lambda device: None
+        ps = [
+            p
+            for group in self.param_groups
+            for p in group["params"]
+            if p.grad is not None
+        ]
+        self._clipper.compute(ps)
+        per_device = {}
+
+        def scale_for(device):
+            if device not in per_device:
+                per_device[device] = self._clipper.out_on(device)
+            return per_device[device]
+
+        return scale_for
+
+
+def _cpu_skip(scale: Optional[torch.Tensor]) -> bool:
+    # the CPU fallback may read the flag: there is no stream to stall
+    return scale is not None and not math.isfinite(float(scale[0]))
+
+
+class FusedSGD(_ClipMixin, torch.optim.Optimizer):
+    """SGD with optional momentum/weight decay, fused on GPU.
+
+    ``max_grad_norm`` (None: off) clips the global gradient norm inside the
+    update kernel; see the module docstring."""
 
     def __init__(
         self,
@@ -44,7 +129,9 @@ class FusedSGD(torch.optim.Optimizer):
         momentum: float = 0.0,
         weight_decay: float = 0.0,
         master_weights: bool = False,
+        max_grad_norm: Optional[float] = None,
     ) -> None:
+        self._init_clip(max_grad_norm)
         defaults = dict(
             lr=lr,
             momentum=momentum,
@@ -62,6 +149,7 @@ class FusedSGD(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None) -> Optional[float]:
         loss = closure() if closure is not None else None
+        scale_for = self._clip_begin()
         for group in self.param_groups:
             lr = group["lr"]
             mom = group["momentum"]
@@ -87,9 +175,10 @@ class FusedSGD(torch.optim.Optimizer):
                 masters = None
                 if use_master and dtype != torch.float32:
                     masters = [self._master_of(p) for p in chunk]
+                scale = scale_for(device)
                 if device.type == "cuda":
                     ext = require_ext()
-                    ext.fused_sgd(
+                    args = (
                         [p.data for p in chunk],
                         grads,
                         bufs if bufs is not None else [],
@@ -98,10 +187,16 @@ class FusedSGD(torch.optim.Optimizer):
                         mom,
                         wd,
                     )
-                else:
+                    if scale is None:
+                        ext.fused_sgd(*args)
+                    else:
+                        ext.fused_sgd(*args, grad_scale=scale)
+                elif not _cpu_skip(scale):
                     # fp32-accumulating fallback, same math as the kernel
                     for i, p in enumerate(chunk):
                         g32 = grads[i].float()
+                        if scale is not None:
+                            g32 = g32 * scale[1]
                         pv = (
                             masters[i]
                             if masters is not None
@@ -118,8 +213,14 @@ class FusedSGD(torch.optim.Optimizer):
         return loss
 
 
-class FusedAdam(torch.optim.Optimizer):
-    """AdamW-style fused optimizer (decoupled weight decay)."""
+class FusedAdam(_ClipMixin, torch.optim.Optimizer):
+    """AdamW-style fused optimizer (decoupled weight decay).
+
+    ``max_grad_norm`` (None: off) clips the global gradient norm inside the
+    update kernel; see the module docstring.  The step counter
+    ``state["step"]`` lives on the host and advances on a skipped step too
+    (the skip is decided on the device and never read back), so after ``k``
+    skipped steps the bias correction is ``k`` steps ahead."""
 
     def __init__(
         self,
@@ -129,7 +230,9 @@ class FusedAdam(torch.optim.Optimizer):
         eps: float = 1e-8,
         weight_decay: float = 0.0,
         master_weights: bool = False,
+        max_grad_norm: Optional[float] = None,
     ) -> None:
+        self._init_clip(max_grad_norm)
         defaults = dict(
             lr=lr,
             betas=betas,
@@ -142,6 +245,7 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None) -> Optional[float]:
         loss = closure() if closure is not None else None
+        scale_for = self._clip_begin()
         for group in self.param_groups:
             lr = group["lr"]
             beta1, beta2 = group["betas"]
@@ -171,9 +275,10 @@ class FusedAdam(torch.optim.Optimizer):
                 bc1 = 1.0 - beta1**step_t
                 bc2 = 1.0 - beta2**step_t
                 grads = [p.grad for p in chunk]
+                scale = scale_for(device)
                 if device.type == "cuda":
                     ext = require_ext()
-                    ext.fused_adam(
+                    args = (
                         [p.data for p in chunk],
                         grads,
                         m,
@@ -187,8 +292,14 @@ class FusedAdam(torch.optim.Optimizer):
                         bc1,
                         bc2,
                     )
-                else:
+                    if scale is None:
+                        ext.fused_adam(*args)
+                    else:
+                        ext.fused_adam(*args, grad_scale=scale)
+                elif not _cpu_skip(scale):
                     gf = [g.float() for g in grads]
+                    if scale is not None:
+                        gf = [g * scale[1] for g in gf]
                     torch._foreach_mul_(m, beta1)
                     torch._foreach_add_(m, gf, alpha=1 - beta1)
                     torch._foreach_mul_(v, beta2)

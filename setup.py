@@ -21,6 +21,7 @@ ext = CUDAExtension(
     sources=[
         os.path.join(CSRC, "bindings.cpp"),
         os.path.join(CSRC, "fused_optim.hip"),
+        os.path.join(CSRC, "grad_norm.hip"),
         os.path.join(CSRC, "layernorm.hip"),
         os.path.join(CSRC, "cross_entropy.hip"),
         os.path.join(CSRC, "rope.hip"),
