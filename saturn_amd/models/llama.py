@@ -8,6 +8,7 @@ Random-init weights, synthetic tokens (no network for checkpoints).
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -33,6 +34,8 @@ class LlamaConfig:
     n_layer: int = 32
     ffn_dim: int = 14336
     rope_theta: float = 500000.0
+    # Mistral-style sliding window: row t attends keys t-window+1 .. t
+    sliding_window: Optional[int] = None
 
 
 PRESETS = {
@@ -43,6 +46,12 @@ PRESETS = {
     "1b-proxy": LlamaConfig(
         n_embd=2048, n_head=32, n_kv_head=8, n_layer=16, ffn_dim=8192
     ),
+    # Mistral-7B-v0.1 (n_ctx 8192 keeps the per-layer fp32 RoPE tables
+    # modest; override it for longer contexts)
+    "mistral-7b": LlamaConfig(
+        vocab_size=32000, n_ctx=8192, n_embd=4096, n_head=32, n_kv_head=8,
+        n_layer=32, ffn_dim=14336, rope_theta=10000.0, sliding_window=4096
+    ),
 }
 
 
@@ -52,6 +61,7 @@ class LlamaAttention(nn.Module):
         self.n_head = cfg.n_head
         self.n_kv = cfg.n_kv_head
         self.head_dim = cfg.n_embd // cfg.n_head
+        self.sliding_window = getattr(cfg, "sliding_window", None)
         E = cfg.n_embd
         self.q_proj = nn.Linear(E, self.n_head * self.head_dim, bias=False)
         self.k_proj = nn.Linear(E, self.n_kv * self.head_dim, bias=False)
@@ -77,7 +87,8 @@ class LlamaAttention(nn.Module):
         q = apply_rope(q, cos, sin, half_style=True)
         k = apply_rope(k, cos, sin, half_style=True)
         o = causal_attention(
-            q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)
+            q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
+            window=self.sliding_window,
         )
         return self.o_proj(o.transpose(1, 2).reshape(B, T, -1))
 
@@ -166,7 +177,7 @@ def get_llama_model(kwargs=None):
     from dataclasses import replace
 
     cfg = PRESETS[kwargs.get("preset", "8b")]
-    for key in ("n_layer", "n_ctx", "vocab_size"):
+    for key in ("n_layer", "n_ctx", "vocab_size", "sliding_window"):
         if key in kwargs:
             cfg = replace(cfg, **{key: kwargs[key]})
     torch.manual_seed(kwargs.get("seed", 0))

@@ -11,6 +11,7 @@ this module alone is the single-process reference semantics.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -37,6 +38,8 @@ class MixtralConfig:
     rope_theta: float = 1000000.0
     n_expert: int = 8
     top_k: int = 2
+    # Mistral-style sliding window: row t attends keys t-window+1 .. t
+    sliding_window: Optional[int] = None
 
 
 PRESETS = {
@@ -197,6 +200,10 @@ def get_mixtral_model(kwargs=None):
     kwargs = kwargs or {}
     if "preset" in kwargs:
         cfg = PRESETS[kwargs["preset"]]
+        if "sliding_window" in kwargs:
+            from dataclasses import replace
+
+            cfg = replace(cfg, sliding_window=kwargs["sliding_window"])
     else:
         cfg = MixtralConfig(
             vocab_size=kwargs.get("vocab_size", 32000),
@@ -208,6 +215,7 @@ def get_mixtral_model(kwargs=None):
             ffn_dim=kwargs.get("ffn_dim", 14336),
             n_expert=kwargs.get("n_expert", 8),
             top_k=kwargs.get("top_k", 2),
+            sliding_window=kwargs.get("sliding_window"),
         )
     torch.manual_seed(kwargs.get("seed", 0))
     return MixtralForCausalLM(cfg)

@@ -123,7 +123,7 @@ struct AttnLds {
   unsigned short p[4][WROWS][KBLK];
 };
 
-template <int D>
+template <int D, bool LO>
 __launch_bounds__(256, 2)
 __global__ void attn_fwd_kernel(const unsigned short* __restrict__ Q,
                                 const unsigned short* __restrict__ K,
@@ -132,7 +132,8 @@ __global__ void attn_fwd_kernel(const unsigned short* __restrict__ Q,
                                 float* __restrict__ LSE, int T, int n_heads,
                                 int n_kv, float scale, int causal,
                                 int kv_len, TStr qs, TStr ks, TStr vs,
-                                TStr os) {
+                                TStr os, const int* __restrict__ KVLO,
+                                long lo_sb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   AttnLds<D>& lds = *reinterpret_cast<AttnLds<D>*>(smem);
 
@@ -171,6 +172,18 @@ __global__ void attn_fwd_kernel(const unsigned short* __restrict__ Q,
   float l_reg[4] = {0.f, 0.f, 0.f, 0.f};
 
   const int kv_end = causal ? (q0_block + QBLK) : T;
+  // ---- kv_lo (LO): row t sees keys lo[t] <= j <= t, lo non-decreasing.
+  // The bound of the block's FIRST row is the smallest of the block, read at
+  // a block-uniform address: every tile below it is skipped by all waves
+  // together, so the barriers stay uniform.
+  int kv_begin = 0;
+  int lo_r[4] = {0, 0, 0, 0};   // bounds of rows qg*4+reg
+  if constexpr (LO) {
+    const int* lo_b = KVLO + b * lo_sb;
+    kv_begin = (lo_b[q0_block] / KBLK) * KBLK;
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) lo_r[reg] = lo_b[q0 + qg * 4 + reg];
+  }
   // ---- async-stage split (guide T14): each thread holds the NEXT tile's
   // K/V rows in registers; the global loads for tile i+1 are issued before
   // tile i's compute so HBM latency hides under the MFMAs, and the LDS
@@ -181,10 +194,12 @@ __global__ void attn_fwd_kernel(const unsigned short* __restrict__ Q,
   for (int c = 0; c < CHUNKS; ++c) {
     const int idx = (c * 256 + threadIdx.x) * 8;
     const int row = idx / D, col = idx % D;
-    stg_k[c] = *reinterpret_cast<const bf16x8*>(Kh + (long)row * ks.st + col);
-    stg_v[c] = *reinterpret_cast<const bf16x8*>(Vh + (long)row * vs.st + col);
+    stg_k[c] = *reinterpret_cast<const bf16x8*>(
+        Kh + (long)(kv_begin + row) * ks.st + col);
+    stg_v[c] = *reinterpret_cast<const bf16x8*>(
+        Vh + (long)(kv_begin + row) * vs.st + col);
   }
-  for (int kv0 = 0; kv0 < kv_end; kv0 += KBLK) {
+  for (int kv0 = kv_begin; kv0 < kv_end; kv0 += KBLK) {
     __syncthreads();  // previous tile fully consumed
 #pragma unroll
     for (int c = 0; c < CHUNKS; ++c) {
@@ -233,6 +248,10 @@ __global__ void attn_fwd_kernel(const unsigned short* __restrict__ Q,
       // ragged T: keys beyond the unpadded length contribute nothing
       if (kv0 + r >= kv_len) s0 = -INFINITY;
       if (kv0 + 16 + r >= kv_len) s1 = -INFINITY;
+      if constexpr (LO) {
+        if (kv0 + r < lo_r[reg]) s0 = -INFINITY;
+        if (kv0 + 16 + r < lo_r[reg]) s1 = -INFINITY;
+      }
       float tm = fmaxf(s0, s1);
 #pragma unroll
       for (int off = 1; off < 16; off <<= 1)
@@ -303,7 +322,7 @@ struct AttnV2Lds {
   unsigned short v[KBLK][D + 8];
 };
 
-template <int D>
+template <int D, bool LO>
 __launch_bounds__(256, 2)
 __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
                                    const unsigned short* __restrict__ K,
@@ -313,7 +332,8 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
                                    int n_heads, int n_kv, float scale,
                                    int causal, int kv_len, TStr qs,
                                    TStr ks, TStr vs,
-                                   TStr os) {
+                                   TStr os, const int* __restrict__ KVLO,
+                                   long lo_sb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   AttnV2Lds<D>& lds = *reinterpret_cast<AttnV2Lds<D>*>(smem);
 
@@ -352,6 +372,15 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
 
   float m_row = -INFINITY, l_row = 0.f;
 
+  // kv_lo (LO): this lane's row bound, and the block's first tile from the
+  // bound of the block's first row (uniform address; see attn_fwd_kernel)
+  int kv_begin = 0, lo_row = 0;
+  if constexpr (LO) {
+    const int* lo_b = KVLO + b * lo_sb;
+    kv_begin = (lo_b[q0_block] / KBLK) * KBLK;
+    lo_row = lo_b[q0 + qr];
+  }
+
   // staging registers (T14 split)
   constexpr int CHUNKS = (KBLK * D) / (256 * 8);
   bf16x8 stg_k[CHUNKS], stg_v[CHUNKS];
@@ -359,12 +388,14 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
   for (int c = 0; c < CHUNKS; ++c) {
     const int idx = (c * 256 + threadIdx.x) * 8;
     const int row = idx / D, col = idx % D;
-    stg_k[c] = *reinterpret_cast<const bf16x8*>(Kh + (long)row * ks.st + col);
-    stg_v[c] = *reinterpret_cast<const bf16x8*>(Vh + (long)row * vs.st + col);
+    stg_k[c] = *reinterpret_cast<const bf16x8*>(
+        Kh + (long)(kv_begin + row) * ks.st + col);
+    stg_v[c] = *reinterpret_cast<const bf16x8*>(
+        Vh + (long)(kv_begin + row) * vs.st + col);
   }
 
   const int kv_end = causal ? (q0_block + 4 * 32) : T;
-  for (int kv0 = 0; kv0 < kv_end; kv0 += KBLK) {
+  for (int kv0 = kv_begin; kv0 < kv_end; kv0 += KBLK) {
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < CHUNKS; ++c) {
@@ -414,6 +445,9 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
       float sv = st[reg] * scale;
       if ((causal && kv0 + key_loc > q_glob) || kv0 + key_loc >= kv_len)
         sv = -INFINITY;
+      if constexpr (LO) {
+        if (kv0 + key_loc < lo_row) sv = -INFINITY;
+      }
       p[reg] = sv;
       tile_max = fmaxf(tile_max, sv);
     }
@@ -569,24 +603,53 @@ static bool dq_is_gkv(int D) { return sw_dq_gkv() && D > 128; }
 
 // The kernel instantiations attn_fwd / attn_bwd launch for a padded T and
 // a head size D in this process, space-separated.
-std::string attn_dispatch(int64_t T, int64_t D) {
+// has_lo: the instantiations taken when a kv_lo bound is given (the names
+// then carry the LO template argument).
+std::string attn_dispatch(int64_t T, int64_t D, bool has_lo) {
   TORCH_CHECK(T > 0 && T % QBLK == 0, "attn_dispatch: T must be a multiple of 64");
   TORCH_CHECK(D == 64 || D == 128 || D == 256, "attn_dispatch: D in {64,128,256}");
   const int t = (int)T, d = (int)D;
   const std::string ds = std::to_string(d);
   const bool gkv = dq_is_gkv(d);
+  const char* lo = has_lo ? ",1>" : ">";
   return std::string(fwd_is_v2(t, d) ? "attn_fwd_v2_kernel<" : "attn_fwd_kernel<") +
-         ds + "> attn_delta_kernel<" + ds + "> attn_bwd_kernel<" + ds + "," +
-         (bwd_is_tr16(d) ? "1," : "0,") + (bwd_is_vl2(d) ? "1>" : "0>") +
+         ds + lo + " attn_delta_kernel<" + ds + "> attn_bwd_kernel<" + ds + "," +
+         (bwd_is_tr16(d) ? "1," : "0,") + (bwd_is_vl2(d) ? "1" : "0") + lo +
          " attn_dq_kernel<" + ds + "," +
-         (!gkv && bwd_is_tr16(d) ? "1," : "0,") + (gkv ? "1>" : "0>");
+         (!gkv && bwd_is_tr16(d) ? "1," : "0,") + (gkv ? "1" : "0") + lo;
+}
+
+// kv_lo: optional int32 [B, T] or [T] (batch stride 0) per-row lower key
+// bound, shared by all heads: row t of batch b attends key j iff
+// kv_lo[b,t] <= j <= t and j < kv_len.  The caller guarantees
+// 0 <= kv_lo[b,t] <= t and kv_lo[b,.] non-decreasing (flash.py is the only
+// producer); nothing here reads the values on the host.
+struct LoArg {
+  const int* ptr;
+  long sb;
+};
+static LoArg lo_arg(const c10::optional<at::Tensor>& kv_lo,
+                    const at::Tensor& q, bool causal, const char* who) {
+  if (!kv_lo.has_value()) return LoArg{nullptr, 0};
+  const at::Tensor& lo = *kv_lo;
+  const int64_t B = q.size(0), T = q.size(2);
+  TORCH_CHECK(causal, who, ": kv_lo requires causal=True");
+  TORCH_CHECK(lo.scalar_type() == at::kInt, who, ": kv_lo must be int32");
+  TORCH_CHECK(lo.is_cuda() && lo.device() == q.device(), who,
+              ": kv_lo must be on q's device");
+  TORCH_CHECK((lo.dim() == 1 && lo.size(0) == T) ||
+                  (lo.dim() == 2 && lo.size(0) == B && lo.size(1) == T),
+              who, ": kv_lo must have shape [T] or [B, T] (padded T)");
+  TORCH_CHECK(lo.is_contiguous(), who, ": kv_lo must be contiguous");
+  return LoArg{lo.data_ptr<int>(), lo.dim() == 2 ? (long)T : 0L};
 }
 
 // ---------------------------------------------------------------------------
 // Host wrapper
 // ---------------------------------------------------------------------------
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                                 bool causal, int64_t kv_len) {
+                                 bool causal, int64_t kv_len,
+                                 c10::optional<at::Tensor> kv_lo) {
   // kv_len < T marks ragged sequences: q/k/v are zero-padded to a 64
   // multiple by the wrapper and keys >= kv_len are masked out in-kernel
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16,
@@ -606,6 +669,7 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   TORCH_CHECK((reinterpret_cast<uintptr_t>(q.data_ptr()) & 15) == 0 &&
               q.stride(2) % 8 == 0 && k.stride(2) % 8 == 0 &&
               v.stride(2) % 8 == 0, "attn_fwd: rows must be 16-B aligned");
+  const LoArg lo = lo_arg(kv_lo, q, causal, "attn_fwd");
 
   // output physically [B, T, H, D]: the model's post-attention
   // transpose(1,2).reshape is then a zero-copy view
@@ -617,10 +681,10 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
 
   if (fwd_is_v2(T, D)) {
     dim3 grid2(B * H, T / 128), block2(256);
-#define LAUNCH_V2(DD)                                                        \
+#define LAUNCH_V2(DD, LO)                                                    \
     do {                                                                     \
       size_t shmem = sizeof(AttnV2Lds<DD>);                                  \
-      hipLaunchKernelGGL((attn_fwd_v2_kernel<DD>), grid2, block2, shmem,     \
+      hipLaunchKernelGGL((attn_fwd_v2_kernel<DD, LO>), grid2, block2, shmem, \
                          stream.stream(),                                    \
                          reinterpret_cast<const unsigned short*>(q.data_ptr()), \
                          reinterpret_cast<const unsigned short*>(k.data_ptr()), \
@@ -628,19 +692,24 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                          reinterpret_cast<unsigned short*>(o.data_ptr()),    \
                          lse.data_ptr<float>(), T, H, Hkv, scale,            \
                          causal ? 1 : 0, (int)kv_len, str_of(q), str_of(k),  \
-                         str_of(v), str_of(o));                              \
+                         str_of(v), str_of(o), lo.ptr, lo.sb);               \
     } while (0)
-    if (D == 64) LAUNCH_V2(64);
-    else LAUNCH_V2(128);
+    if (lo.ptr) {
+      if (D == 64) LAUNCH_V2(64, true);
+      else LAUNCH_V2(128, true);
+    } else {
+      if (D == 64) LAUNCH_V2(64, false);
+      else LAUNCH_V2(128, false);
+    }
 #undef LAUNCH_V2
     return {o, lse};
   }
   dim3 grid(B * H, T / QBLK), block(256);
 
-#define LAUNCH(DD)                                                          \
+#define LAUNCH(DD, LO)                                                      \
   do {                                                                      \
     size_t shmem = sizeof(AttnLds<DD>);                                     \
-    hipLaunchKernelGGL((attn_fwd_kernel<DD>), grid, block, shmem,           \
+    hipLaunchKernelGGL((attn_fwd_kernel<DD, LO>), grid, block, shmem,       \
                        stream.stream(),                                     \
                        reinterpret_cast<const unsigned short*>(q.data_ptr()), \
                        reinterpret_cast<const unsigned short*>(k.data_ptr()), \
@@ -648,12 +717,18 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                        reinterpret_cast<unsigned short*>(o.data_ptr()),     \
                        lse.data_ptr<float>(), T, H, Hkv, scale,             \
                        causal ? 1 : 0, (int)kv_len, str_of(q), str_of(k),   \
-                       str_of(v), str_of(o));                               \
+                       str_of(v), str_of(o), lo.ptr, lo.sb);                \
   } while (0)
 
-  if (D == 64) LAUNCH(64);
-  else if (D == 128) LAUNCH(128);
-  else LAUNCH(256);
+  if (lo.ptr) {
+    if (D == 64) LAUNCH(64, true);
+    else if (D == 128) LAUNCH(128, true);
+    else LAUNCH(256, true);
+  } else {
+    if (D == 64) LAUNCH(64, false);
+    else if (D == 128) LAUNCH(128, false);
+    else LAUNCH(256, false);
+  }
 #undef LAUNCH
   return {o, lse};
 }
@@ -692,6 +767,15 @@ struct AttnBwdLds {
   float lse_t[bwd::QT];
   float delta_t[bwd::QT];
 };
+// with kv_lo: the q tile's row bounds beside lse_t / delta_t (a struct of its
+// own, so the plain instantiations keep their LDS size)
+template <int D, bool HASV>
+struct AttnBwdLdsLo : AttnBwdLds<D, HASV> {
+  int lo_t[bwd::QT];
+};
+template <int D, bool HASV, bool LO>
+using AttnBwdLdsT = typename std::conditional<LO, AttnBwdLdsLo<D, HASV>,
+                                              AttnBwdLds<D, HASV>>::type;
 
 
 // delta = rowsum(dO * O) for the FA2 backward, one fused pass.  The torch
@@ -736,7 +820,7 @@ __global__ void attn_delta_kernel(const unsigned short* __restrict__ dO,
   }
 }
 
-template <int D, bool TR16, bool VL2>
+template <int D, bool TR16, bool VL2, bool LO>
 __launch_bounds__(256, 2)
 __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
                                 const unsigned short* __restrict__ Q,
@@ -751,11 +835,13 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
                                 int n_kv, float scale, int causal,
                                 int kv_len, TStr dos,
                                 TStr qs, TStr ks, TStr vs,
-                                TStr dks, TStr dvs) {
+                                TStr dks, TStr dvs,
+                                const int* __restrict__ KVLO, long lo_sb) {
   using namespace bwd;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool HASV = (D <= 128) && !VL2;  // V tile LDS-resident?
-  AttnBwdLds<D, HASV>& lds = *reinterpret_cast<AttnBwdLds<D, HASV>*>(smem);
+  AttnBwdLdsT<D, HASV, LO>& lds =
+      *reinterpret_cast<AttnBwdLdsT<D, HASV, LO>*>(smem);
 
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
@@ -772,6 +858,8 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
   const unsigned short* dOh = dO + b * dos.sb + h * dos.sh;
   const float* lse_h = LSE + bh * (long)T;
   const float* del_h = DELTA + bh * (long)T;
+  const int* lo_b = nullptr;
+  if constexpr (LO) lo_b = KVLO + b * lo_sb;
 
   // ---- stage the K tile once (and V when it fits; see struct comment)
   {
@@ -799,6 +887,12 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
 
   const int q_start = causal ? kv0 : 0;
   for (int q0 = q_start; q0 < T; q0 += QT) {
+    // kv_lo is non-decreasing: once a q tile's FIRST row starts past this
+    // block's last key, no later row sees the block.  One uniform address,
+    // so all waves leave together, ahead of the barrier.
+    if constexpr (LO) {
+      if (lo_b[q0] > kv0 + KB - 1) break;
+    }
     // ---- stage Q / dO tiles + lse/delta
     __syncthreads();
     {
@@ -817,6 +911,7 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
       if (threadIdx.x < QT) {
         lds.lse_t[threadIdx.x] = lse_h[q0 + threadIdx.x];
         lds.delta_t[threadIdx.x] = del_h[q0 + threadIdx.x];
+        if constexpr (LO) lds.lo_t[threadIdx.x] = lo_b[q0 + threadIdx.x];
       }
     }
     __syncthreads();
@@ -850,7 +945,9 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
         const int key_glob = kv0 + wid * 16 + key_loc;
         const int q_glob = q0 + n * 16 + r;
         float p = 0.f;
-        if ((!causal || q_glob >= key_glob) && key_glob < kv_len) {
+        bool seen = (!causal || q_glob >= key_glob) && key_glob < kv_len;
+        if constexpr (LO) seen = seen && key_glob >= lds.lo_t[n * 16 + r];
+        if (seen) {
           p = __expf(scale * st[reg] - lds.lse_t[n * 16 + r]);
         }
         const float dsv = p * (dpt[reg] - lds.delta_t[n * 16 + r]) * scale;
@@ -960,7 +1057,7 @@ struct AttnDqLds {
   float delta_t[dq::QB];
 };
 
-template <int D, bool TR16, bool GKV>
+template <int D, bool TR16, bool GKV, bool LO>
 __launch_bounds__(256, GKV ? 3 : (D <= 128 ? 2 : 1))
 __global__ void attn_dq_kernel(const unsigned short* __restrict__ dO,
                                const unsigned short* __restrict__ Q,
@@ -971,7 +1068,8 @@ __global__ void attn_dq_kernel(const unsigned short* __restrict__ dO,
                                unsigned short* __restrict__ dQ16, int T,
                                int n_heads, int n_kv, float scale, int causal,
                                int kv_len, TStr dos, TStr qs, TStr ks,
-                               TStr vs, TStr dqs) {
+                               TStr vs, TStr dqs,
+                               const int* __restrict__ KVLO, long lo_sb) {
   using namespace dq;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   AttnDqLds<D, GKV>& lds = *reinterpret_cast<AttnDqLds<D, GKV>*>(smem);
@@ -1018,7 +1116,15 @@ __global__ void attn_dq_kernel(const unsigned short* __restrict__ dO,
   for (int dt = 0; dt < D / 16; ++dt) acc[dt] = {0.f, 0.f, 0.f, 0.f};
 
   const int k_end = causal ? (q0 + QB < T ? q0 + QB : T) : T;
-  for (int k0 = 0; k0 < k_end; k0 += KT) {
+  // kv_lo (LO): this lane's q row bound; the key loop starts at the tile of
+  // the block's first row's bound (uniform address; see attn_fwd_kernel)
+  int k_begin = 0, lo_q = 0;
+  if constexpr (LO) {
+    const int* lo_b = KVLO + b * lo_sb;
+    k_begin = (lo_b[q0] / KT) * KT;
+    lo_q = lo_b[q0 + wid * 16 + r];
+  }
+  for (int k0 = k_begin; k0 < k_end; k0 += KT) {
     __syncthreads();  // previous tile fully consumed (also orders staging)
     {
       constexpr int CHUNKS = (KT * D) / (256 * 8);
@@ -1077,8 +1183,9 @@ __global__ void attn_dq_kernel(const unsigned short* __restrict__ dO,
       for (int reg = 0; reg < 4; ++reg) {
         const int key_glob = k0 + n * 16 + qg * 4 + reg;
         float p = 0.f;
-        if ((!causal || q_glob >= key_glob) && key_glob < kv_len)
-          p = __expf(scale * st[reg] - l_q);
+        bool seen = (!causal || q_glob >= key_glob) && key_glob < kv_len;
+        if constexpr (LO) seen = seen && key_glob >= lo_q;
+        if (seen) p = __expf(scale * st[reg] - l_q);
         ds_sub[n][reg] = p * (dpt[reg] - d_q) * scale;
       }
     }
@@ -1143,7 +1250,8 @@ __global__ void attn_dq_kernel(const unsigned short* __restrict__ dO,
 
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  at::Tensor v, at::Tensor o, at::Tensor lse,
-                                 bool causal, int64_t kv_len) {
+                                 bool causal, int64_t kv_len,
+                                 c10::optional<at::Tensor> kv_lo) {
   using namespace bwd;
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16);
   const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2),
@@ -1158,6 +1266,16 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
               v.stride(3) == 1, "attn_bwd: innermost dim must be dense");
   TORCH_CHECK(dout.stride(2) % 8 == 0 && q.stride(2) % 8 == 0 &&
               k.stride(2) % 8 == 0 && v.stride(2) % 8 == 0);
+  const LoArg lo = lo_arg(kv_lo, q, causal, "attn_bwd");
+  if (lo.ptr) {
+    // the kv_lo instantiations exist for the default dispatch only
+    TORCH_CHECK(sw_tr16(), "attn_bwd: kv_lo is not built for "
+                "SAMD_ATTN_BWD_TR16=0; unset the switch");
+    TORCH_CHECK(!sw_vl2(), "attn_bwd: kv_lo is not built for "
+                "SAMD_ATTN_BWD_VL2=1; unset the switch");
+    TORCH_CHECK(!sw_dq_gkv(), "attn_bwd: kv_lo is not built for "
+                "SAMD_ATTN_DQ_GKV=1; unset the switch");
+  }
 
   auto delta = at::empty({B, H, T}, q.options().dtype(at::kFloat));
   // grads physically [B, T, H, D] (matches the projection layout upstream,
@@ -1194,7 +1312,18 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
     scale, causal ? 1 : 0, (int)kv_len, str_of(dout), str_of(q),             \
     str_of(k), str_of(v),                                                    \
     gqa ? str_of(dk_f32) : str_of(dk),                                       \
-    gqa ? str_of(dv_f32) : str_of(dv)
+    gqa ? str_of(dv_f32) : str_of(dv), lo.ptr, lo.sb
+
+#define DQ_ARGS                                                              \
+    stream.stream(),                                                         \
+    reinterpret_cast<const unsigned short*>(dout.data_ptr()),                \
+    reinterpret_cast<const unsigned short*>(q.data_ptr()),                   \
+    reinterpret_cast<const unsigned short*>(k.data_ptr()),                   \
+    reinterpret_cast<const unsigned short*>(v.data_ptr()),                   \
+    lse.data_ptr<float>(), delta.data_ptr<float>(),                          \
+    reinterpret_cast<unsigned short*>(dq.data_ptr()),                        \
+    T, H, Hkv, scale, causal ? 1 : 0, (int)kv_len,                           \
+    str_of(dout), str_of(q), str_of(k), str_of(v), str_of(dq), lo.ptr, lo.sb
 
 #define LAUNCH_B(DD)                                                         \
   do {                                                                       \
@@ -1214,11 +1343,18 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                        : sizeof(AttnDqLds<DD, false>);                       \
     static bool dq_attr_##DD = [] {                                          \
       hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(&attn_dq_kernel<DD, false, false>),  \
+          reinterpret_cast<const void*>(                                     \
+              &attn_dq_kernel<DD, false, false, false>),                     \
           hipFuncAttributeMaxDynamicSharedMemorySize,                        \
           (int)sizeof(AttnDqLds<DD, false>));                                \
       hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(&attn_dq_kernel<DD, true, false>),   \
+          reinterpret_cast<const void*>(                                     \
+              &attn_dq_kernel<DD, true, false, false>),                      \
+          hipFuncAttributeMaxDynamicSharedMemorySize,                        \
+          (int)sizeof(AttnDqLds<DD, false>));                                \
+      hipFuncSetAttribute(                                                   \
+          reinterpret_cast<const void*>(                                     \
+              &attn_dq_kernel<DD, (DD <= 128), false, true>),                \
           hipFuncAttributeMaxDynamicSharedMemorySize,                        \
           (int)sizeof(AttnDqLds<DD, false>));                                \
       return true;                                                           \
@@ -1226,82 +1362,72 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
     (void)dq_attr_##DD;                                                      \
     {                                                                        \
       dim3 qgrid(B * H, T / dq::QB), qblock(256);                            \
-      if (gkv)                                                               \
-        hipLaunchKernelGGL((attn_dq_kernel<DD, false, true>), qgrid,         \
-                           qblock, SH_DQ, stream.stream(),                   \
-                           reinterpret_cast<const unsigned short*>(dout.data_ptr()), \
-                           reinterpret_cast<const unsigned short*>(q.data_ptr()), \
-                           reinterpret_cast<const unsigned short*>(k.data_ptr()), \
-                           reinterpret_cast<const unsigned short*>(v.data_ptr()), \
-                           lse.data_ptr<float>(), delta.data_ptr<float>(),   \
-                           reinterpret_cast<unsigned short*>(dq.data_ptr()), \
-                           T, H, Hkv, scale, causal ? 1 : 0, (int)kv_len,   \
-                           str_of(dout), str_of(q), str_of(k), str_of(v),    \
-                           str_of(dq));                                      \
+      if (lo.ptr)                                                            \
+        hipLaunchKernelGGL((attn_dq_kernel<DD, (DD <= 128), false, true>),   \
+                           qgrid, qblock, SH_DQ, DQ_ARGS);                   \
+      else if (gkv)                                                          \
+        hipLaunchKernelGGL((attn_dq_kernel<DD, false, true, false>), qgrid,  \
+                           qblock, SH_DQ, DQ_ARGS);                          \
       else if (bwd_is_tr16(DD))                                              \
-        hipLaunchKernelGGL((attn_dq_kernel<DD, true, false>), qgrid,         \
-                           qblock, SH_DQ, stream.stream(),                   \
-                           reinterpret_cast<const unsigned short*>(dout.data_ptr()), \
-                           reinterpret_cast<const unsigned short*>(q.data_ptr()), \
-                           reinterpret_cast<const unsigned short*>(k.data_ptr()), \
-                           reinterpret_cast<const unsigned short*>(v.data_ptr()), \
-                           lse.data_ptr<float>(), delta.data_ptr<float>(),   \
-                           reinterpret_cast<unsigned short*>(dq.data_ptr()), \
-                           T, H, Hkv, scale, causal ? 1 : 0, (int)kv_len,   \
-                           str_of(dout), str_of(q), str_of(k), str_of(v),    \
-                           str_of(dq));                                      \
+        hipLaunchKernelGGL((attn_dq_kernel<DD, true, false, false>), qgrid,  \
+                           qblock, SH_DQ, DQ_ARGS);                          \
       else                                                                   \
-        hipLaunchKernelGGL((attn_dq_kernel<DD, false, false>), qgrid,        \
-                           qblock, SH_DQ, stream.stream(),                   \
-                           reinterpret_cast<const unsigned short*>(dout.data_ptr()), \
-                           reinterpret_cast<const unsigned short*>(q.data_ptr()), \
-                           reinterpret_cast<const unsigned short*>(k.data_ptr()), \
-                           reinterpret_cast<const unsigned short*>(v.data_ptr()), \
-                           lse.data_ptr<float>(), delta.data_ptr<float>(),   \
-                           reinterpret_cast<unsigned short*>(dq.data_ptr()), \
-                           T, H, Hkv, scale, causal ? 1 : 0, (int)kv_len,   \
-                           str_of(dout), str_of(q), str_of(k), str_of(v),    \
-                           str_of(dq));                                      \
+        hipLaunchKernelGGL((attn_dq_kernel<DD, false, false, false>), qgrid, \
+                           qblock, SH_DQ, DQ_ARGS);                          \
     }                                                                        \
     const bool tr = bwd_is_tr16(DD);                                         \
     const bool vl2 = bwd_is_vl2(DD);                                         \
     constexpr size_t SH_V = sizeof(AttnBwdLds<DD, (DD <= 128)>);             \
     constexpr size_t SH_N = sizeof(AttnBwdLds<DD, false>);                   \
-    size_t shmem = vl2 ? SH_N : SH_V;                                        \
+    constexpr size_t SH_LO = sizeof(AttnBwdLdsLo<DD, (DD <= 128)>);          \
+    size_t shmem = lo.ptr ? SH_LO : (vl2 ? SH_N : SH_V);                     \
     static bool attr_set_##DD = [] {                                         \
       hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(&attn_bwd_kernel<DD, false, false>), \
+          reinterpret_cast<const void*>(                                     \
+              &attn_bwd_kernel<DD, false, false, false>),                    \
           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_V);            \
       hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(&attn_bwd_kernel<DD, true, false>),  \
+          reinterpret_cast<const void*>(                                     \
+              &attn_bwd_kernel<DD, true, false, false>),                     \
           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_V);            \
       hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(&attn_bwd_kernel<DD, false, true>),  \
+          reinterpret_cast<const void*>(                                     \
+              &attn_bwd_kernel<DD, false, true, false>),                     \
           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_N);            \
       hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(&attn_bwd_kernel<DD, true, true>),   \
+          reinterpret_cast<const void*>(                                     \
+              &attn_bwd_kernel<DD, true, true, false>),                      \
           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_N);            \
+      hipFuncSetAttribute(                                                   \
+          reinterpret_cast<const void*>(                                     \
+              &attn_bwd_kernel<DD, (DD <= 128), false, true>),               \
+          hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_LO);           \
       return true;                                                           \
     }();                                                                     \
     (void)attr_set_##DD;                                                     \
-    if (tr && vl2)                                                           \
-      hipLaunchKernelGGL((attn_bwd_kernel<DD, true, true>), grid, block,     \
-                         shmem, BWD_ARGS);                                   \
+    if (lo.ptr)                                                              \
+      hipLaunchKernelGGL((attn_bwd_kernel<DD, (DD <= 128), false, true>),    \
+                         grid, block, shmem, BWD_ARGS);                      \
+    else if (tr && vl2)                                                      \
+      hipLaunchKernelGGL((attn_bwd_kernel<DD, true, true, false>), grid,     \
+                         block, shmem, BWD_ARGS);                            \
     else if (tr)                                                             \
-      hipLaunchKernelGGL((attn_bwd_kernel<DD, true, false>), grid, block,    \
-                         shmem, BWD_ARGS);                                   \
+      hipLaunchKernelGGL((attn_bwd_kernel<DD, true, false, false>), grid,    \
+                         block, shmem, BWD_ARGS);                            \
     else if (vl2)                                                            \
-      hipLaunchKernelGGL((attn_bwd_kernel<DD, false, true>), grid, block,    \
-                         shmem, BWD_ARGS);                                   \
+      hipLaunchKernelGGL((attn_bwd_kernel<DD, false, true, false>), grid,    \
+                         block, shmem, BWD_ARGS);                            \
     else                                                                     \
-      hipLaunchKernelGGL((attn_bwd_kernel<DD, false, false>), grid, block,   \
-                         shmem, BWD_ARGS);                                   \
+      hipLaunchKernelGGL((attn_bwd_kernel<DD, false, false, false>), grid,   \
+                         block, shmem, BWD_ARGS);                            \
   } while (0)
 
   if (D == 64) LAUNCH_B(64);
   else if (D == 128) LAUNCH_B(128);
   else LAUNCH_B(256);
 #undef LAUNCH_B
+#undef DQ_ARGS
+#undef BWD_ARGS
   if (gqa) return {dq, dk_f32.to(at::kBFloat16), dv_f32.to(at::kBFloat16)};
   return {dq, dk, dv};
 }

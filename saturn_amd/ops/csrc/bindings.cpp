@@ -33,11 +33,13 @@ void rope_apply(at::Tensor y, at::Tensor x, at::Tensor cos_t, at::Tensor sin_t,
 at::Tensor gelu_fwd(at::Tensor x);
 at::Tensor gelu_bwd(at::Tensor dy, at::Tensor x);
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                                 bool causal, int64_t kv_len);
+                                 bool causal, int64_t kv_len,
+                                 c10::optional<at::Tensor> kv_lo);
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  at::Tensor v, at::Tensor o, at::Tensor lse,
-                                 bool causal, int64_t kv_len);
-std::string attn_dispatch(int64_t T, int64_t D);
+                                 bool causal, int64_t kv_len,
+                                 c10::optional<at::Tensor> kv_lo);
+std::string attn_dispatch(int64_t T, int64_t D, bool has_lo);
 at::Tensor add3(at::Tensor a, at::Tensor b, at::Tensor c);
 at::Tensor swiglu_fwd(at::Tensor gate, at::Tensor up);
 std::vector<at::Tensor> swiglu_bwd(at::Tensor dout, at::Tensor gate,
@@ -107,14 +109,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gelu_bwd", &samd::gelu_bwd, "fused tanh-approx GELU backward");
   m.def("attn_fwd", &samd::attn_fwd, "fused flash attention forward",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
-        py::arg("kv_len") = -1);
+        py::arg("kv_len") = -1, py::arg("kv_lo") = py::none());
   m.def("attn_dispatch", &samd::attn_dispatch,
         "kernel instantiations attn_fwd/attn_bwd launch for (padded T, D)",
-        py::arg("T"), py::arg("D"));
+        py::arg("T"), py::arg("D"), py::arg("has_lo") = false);
   m.def("attn_bwd", &samd::attn_bwd, "fused flash attention backward",
         py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o"), py::arg("lse"), py::arg("causal"),
-        py::arg("kv_len") = -1);
+        py::arg("kv_len") = -1, py::arg("kv_lo") = py::none());
   m.def("add3", &samd::add3, "fused 3-way residual add");
   m.def("swiglu_fwd", &samd::swiglu_fwd, "fused silu(gate)*up");
   m.def("swiglu_bwd", &samd::swiglu_bwd, "fused SwiGLU backward");

@@ -34,7 +34,8 @@ namespace samd {
 // attention.hip / mlp_bwd.hip
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  at::Tensor v, at::Tensor o, at::Tensor lse,
-                                 bool causal, int64_t kv_len);
+                                 bool causal, int64_t kv_len,
+                                 c10::optional<at::Tensor> kv_lo);
 std::vector<at::Tensor> mlp_act_bwd(at::Tensor d_act, at::Tensor pre,
                                     bool want_dT, bool want_aT);
 // rope.hip
@@ -266,7 +267,7 @@ std::vector<at::Tensor> gptj_branches_bwd(
   at::Tensor dq_r, dk_r, dv;
   {
     auto r = attn_bwd(d_o.view({B, T, H, D}).permute({0, 2, 1, 3}), q, k, v, o,
-                      lse, true, T);
+                      lse, true, T, c10::nullopt);
     dq_r = r[0].permute({0, 2, 1, 3});
     dk_r = r[1].permute({0, 2, 1, 3});
     dv = r[2].permute({0, 2, 1, 3});

@@ -5,6 +5,11 @@
 falls back to the explicit-GEMM math composition (rocBLAS GEMMs + softmax —
 no Triton, no aotriton) and WARNS once: measurements taken on the fallback
 are not this framework's attention numbers.
+
+Causal attention takes an optional per-row lower key bound ``kv_lo``: row
+``t`` of batch ``b`` attends key ``j`` iff ``kv_lo[b, t] <= j <= t``.  A
+sliding window (``window_lo``) and packed documents (``document_lo``) are
+both such bounds; the kernels skip the key tiles no row of a block sees.
 """
 
 from __future__ import annotations
@@ -19,6 +24,75 @@ log = logging.getLogger(__name__)
 _warned = False
 
 
+_window_lo_cache: dict = {}
+
+
+def window_lo(T: int, window: int, device) -> torch.Tensor:
+    """int32 [T]: ``max(0, t - window + 1)`` — row t sees ``window`` keys
+    including itself (the Hugging Face Mistral convention).  Cached per
+    (T, window, device); treat the result as read-only."""
+    if window < 1:
+        raise ValueError(f"window must be >= 1, got {window}")
+    key = (int(T), int(window), torch.device(device))
+    lo = _window_lo_cache.get(key)
+    if lo is None:
+        t = torch.arange(T, dtype=torch.int32, device=device)
+        lo = (t - (int(window) - 1)).clamp_(min=0)
+        _window_lo_cache[key] = lo
+    return lo
+
+
+def document_lo(input_ids: torch.Tensor, sep_id: int) -> torch.Tensor:
+    """int32 [B, T]: the first position of the document each token belongs
+    to, for rows that pack several documents.  A document starts at position
+    0 and after every ``sep_id`` token; the separator belongs to the document
+    it ends.  Built on ``input_ids``' device from a cummax with no host
+    read, so a training step still captures into a hipGraph."""
+    if input_ids.dim() != 2:
+        raise ValueError("document_lo: input_ids must be [B, T]")
+    B, T = input_ids.shape
+    pos = torch.arange(T, device=input_ids.device).expand(B, T)
+    starts = torch.zeros_like(pos)
+    starts[:, 1:] = torch.where(input_ids[:, :-1] == sep_id, pos[:, 1:], 0)
+    return starts.cummax(dim=-1).values.to(torch.int32)
+
+
+def resolve_lo(T: int, device, causal: bool, window=None, kv_lo=None):
+    """The bound a (window, kv_lo) pair asks for at length T, or None when
+    it is the plain causal triangle.  An explicit ``kv_lo`` is brought into
+    the kernels' contract (0 <= lo[t] <= t, non-decreasing) on the device."""
+    if window is None and kv_lo is None:
+        return None
+    if not causal:
+        raise ValueError("window / kv_lo need causal=True")
+    if window is not None:
+        if int(window) != window or window < 1:
+            raise ValueError(f"window must be an int >= 1, got {window!r}")
+        window = None if window >= T else int(window)
+    if kv_lo is None:
+        return None if window is None else window_lo(T, window, device)
+    if kv_lo.dtype != torch.int32:
+        raise ValueError(f"kv_lo must be int32, got {kv_lo.dtype}")
+    if kv_lo.dim() not in (1, 2) or kv_lo.shape[-1] != T:
+        raise ValueError(
+            f"kv_lo must be [T] or [B, T] with T={T}, got {tuple(kv_lo.shape)}")
+    if kv_lo.device != torch.device(device):
+        raise ValueError(f"kv_lo is on {kv_lo.device}, q on {device}")
+    t = torch.arange(T, dtype=torch.int32, device=device)
+    lo = torch.minimum(kv_lo.clamp(min=0), t).cummax(dim=-1).values
+    if window is not None:
+        lo = torch.maximum(lo, window_lo(T, window, device))
+    return lo.to(torch.int32).contiguous()
+
+
+def lo_mask(kv_lo: torch.Tensor) -> torch.Tensor:
+    """bool [T, T] or [B, 1, T, T]: may row t see key j (lo[t] <= j <= t)?"""
+    T = kv_lo.shape[-1]
+    j = torch.arange(T, device=kv_lo.device)
+    ok = (j >= kv_lo.long().unsqueeze(-1)) & (j <= j[:, None])
+    return ok.unsqueeze(1) if ok.dim() == 3 else ok
+
+
 def _pad_t64(t: torch.Tensor) -> torch.Tensor:
     """Zero-pad the T dim (dim -2) up to a multiple of 64."""
     pad = (-t.shape[-2]) % 64
@@ -29,17 +103,24 @@ def _pad_t64(t: torch.Tensor) -> torch.Tensor:
 
 class _FlashFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal):
+    def forward(ctx, q, k, v, causal, kv_lo=None):
         ext = require_ext()
         T = q.shape[-2]
+        if T % 64 and kv_lo is not None:
+            # padded rows get the last real key as their bound: still
+            # non-decreasing and <= t, and no padded row is empty (an empty
+            # row would put NaN into LSE and, through exp(s - lse) * 0,
+            # into dK/dV)
+            kv_lo = torch.nn.functional.pad(kv_lo, (0, (-T) % 64), value=T - 1)
         if T % 64:
             # ragged T (ViT's 197, BERT's raw lengths): zero-pad to the
             # kernels' 64-row tiles; padded KEYS are masked in-kernel via
             # kv_len and padded q rows are sliced off below (their zero
             # dO rows contribute exactly 0 to dK/dV in backward)
             q, k, v = _pad_t64(q), _pad_t64(k), _pad_t64(v)
-        o, lse = ext.attn_fwd(q, k, v, causal, T)
+        o, lse = ext.attn_fwd(q, k, v, causal, T, kv_lo=kv_lo)
         ctx.save_for_backward(q, k, v, o, lse)
+        ctx.kv_lo = kv_lo  # int32, no gradient
         ctx.causal = causal
         ctx.t_real = T
         return o[:, :, :T] if T % 64 else o
@@ -51,10 +132,11 @@ class _FlashFn(torch.autograd.Function):
         T = ctx.t_real
         if hasattr(ext, "attn_bwd"):
             do = _pad_t64(_dense_rows(do)) if T % 64 else _dense_rows(do)
-            dq, dk, dv = ext.attn_bwd(do, q, k, v, o, lse, ctx.causal, T)
+            dq, dk, dv = ext.attn_bwd(do, q, k, v, o, lse, ctx.causal, T,
+                                      kv_lo=ctx.kv_lo)
             if T % 64:
                 dq, dk, dv = dq[:, :, :T], dk[:, :, :T], dv[:, :, :T]
-            return dq, dk, dv, None
+            return dq, dk, dv, None, None
         # Analytic FA2 backward composed from rocBLAS GEMMs (recompute P
         # from the saved LSE; O(T^2) transient, fp32 math).  The fused HIP
         # backward kernel replaces this path when built.
@@ -65,6 +147,8 @@ class _FlashFn(torch.autograd.Function):
         if ctx.causal:
             T = q.shape[-2]
             mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
+            if ctx.kv_lo is not None:
+                mask = mask & lo_mask(ctx.kv_lo)
             s = s.masked_fill(~mask, float("-inf"))
         p = torch.exp(s - lse.unsqueeze(-1))
         dv = torch.matmul(p.transpose(-1, -2), dof)
@@ -73,7 +157,7 @@ class _FlashFn(torch.autograd.Function):
         ds = p * (dp - delta) * scale
         dq = torch.matmul(ds, kf)
         dk = torch.matmul(ds.transpose(-1, -2), qf)
-        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None
+        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None
 
 
 def _kernel_supported(q) -> bool:
@@ -97,13 +181,25 @@ def _dense_rows(t):
     return t.clone(memory_format=torch.contiguous_format)
 
 
-def flash_attention(q, k, v, causal: bool = True) -> torch.Tensor:
-    """q,k,v: [B, H, T, D] bf16/fp16 contiguous (GQA: H_kv may divide H)."""
+def flash_attention(q, k, v, causal: bool = True, window=None,
+                    kv_lo=None) -> torch.Tensor:
+    """q,k,v: [B, H, T, D] bf16/fp16 contiguous (GQA: H_kv may divide H).
+
+    ``window`` (int >= 1): row t sees keys max(0, t-window+1) .. t.
+    ``kv_lo`` (int32 [T] or [B, T] on q's device): row t sees keys
+    kv_lo[b,t] .. t; shared by all heads.  Given both, the bound is the
+    elementwise maximum.  Both need ``causal=True`` (ValueError otherwise);
+    ``window >= T`` without ``kv_lo`` is the plain causal path."""
+    lo = resolve_lo(q.shape[-2], q.device, causal, window, kv_lo)
     ext = require_ext()
     if hasattr(ext, "attn_fwd") and _kernel_supported(q):
         # GQA is native in the kernels: kv may keep fewer heads
+        if lo is None:
+            return _FlashFn.apply(
+                _dense_rows(q), _dense_rows(k), _dense_rows(v), causal
+            )
         return _FlashFn.apply(
-            _dense_rows(q), _dense_rows(k), _dense_rows(v), causal
+            _dense_rows(q), _dense_rows(k), _dense_rows(v), causal, lo
         )
     global _warned
     if not _warned:
@@ -118,4 +214,4 @@ def flash_attention(q, k, v, causal: bool = True) -> torch.Tensor:
         rep = q.shape[1] // k.shape[1]
         k = k.repeat_interleave(rep, dim=1)
         v = v.repeat_interleave(rep, dim=1)
-    return attention_math(q, k, v, causal=causal)
+    return attention_math(q, k, v, causal=causal, kv_lo=lo)

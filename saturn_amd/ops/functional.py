@@ -243,44 +243,64 @@ def apply_rope(
 # fallback below (explicit GEMMs + softmax, fp32 accum like the reference's
 # GPTJ.py:164-191) is used on CPU and as the numerics reference.
 # ---------------------------------------------------------------------------
-def attention_math(q, k, v, causal: bool = True) -> torch.Tensor:
-    """q,k,v: [B, H, T, D].  fp32 score math, returns q.dtype."""
+def attention_math(q, k, v, causal: bool = True, kv_lo=None) -> torch.Tensor:
+    """q,k,v: [B, H, T, D].  fp32 score math, returns q.dtype.
+
+    ``kv_lo`` (integer [T] or [B, T], needs ``causal``): row t sees keys
+    kv_lo[b,t] .. t instead of 0 .. t."""
+    if kv_lo is not None and not causal:
+        raise ValueError("kv_lo needs causal=True")
     scale = 1.0 / (q.shape[-1] ** 0.5)
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
     if causal:
         T = q.shape[-2]
         mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
+        if kv_lo is not None:
+            from saturn_amd.ops.flash import lo_mask
+
+            mask = mask & lo_mask(kv_lo)
         s = s.masked_fill(~mask, float("-inf"))
     p = torch.softmax(s, dim=-1)
     return torch.matmul(p, v.float()).to(q.dtype)
 
 
-def _attention_core(q, k, v, causal: bool) -> torch.Tensor:
-    if q.is_cuda:
-        from saturn_amd.ops import flash  # local import: optional kernel
+def _attention_core(q, k, v, causal: bool, window=None, kv_lo=None) -> torch.Tensor:
+    from saturn_amd.ops import flash  # local import: optional kernel
 
-        return flash.flash_attention(q, k, v, causal=causal)
+    if q.is_cuda:
+        return flash.flash_attention(q, k, v, causal=causal, window=window,
+                                     kv_lo=kv_lo)
     if k.shape[1] != q.shape[1]:
         rep = q.shape[1] // k.shape[1]
         k = k.repeat_interleave(rep, dim=1)
         v = v.repeat_interleave(rep, dim=1)
-    return attention_math(q, k, v, causal=causal)
+    lo = flash.resolve_lo(q.shape[-2], q.device, causal, window, kv_lo)
+    return attention_math(q, k, v, causal=causal, kv_lo=lo)
 
 
-def _attention(q, k, v, causal: bool) -> torch.Tensor:
+def _attention(q, k, v, causal: bool, window=None, kv_lo=None) -> torch.Tensor:
     from saturn_amd.parallel.sequence import sp_attention, sp_world
 
     if sp_world() > 1:
         # Ulysses: all-to-all seq-shard <-> head-shard around the full-
-        # sequence kernel (exact causal masking on the gathered sequence)
-        return sp_attention(q, k, v, lambda a, b, c: _attention_core(a, b, c, causal))
-    return _attention_core(q, k, v, causal)
+        # sequence kernel (exact causal masking on the gathered sequence;
+        # the window bound is built there, from the gathered length)
+        return sp_attention(
+            q, k, v,
+            lambda a, b, c: _attention_core(a, b, c, causal, window, kv_lo))
+    return _attention_core(q, k, v, causal, window, kv_lo)
 
 
-def causal_attention(q, k, v) -> torch.Tensor:
+def causal_attention(q, k, v, window=None, kv_lo=None) -> torch.Tensor:
     """Dispatch: fused CDNA4 flash kernel on GPU (when built), math path on
-    CPU.  Handles GQA (k/v with fewer heads) by expansion."""
-    return _attention(q, k, v, causal=True)
+    CPU.  Handles GQA (k/v with fewer heads) by expansion.
+
+    ``window`` / ``kv_lo``: sliding window and per-row lower key bound, as
+    in ``flash.flash_attention``.  Under Ulysses sequence parallelism the
+    bound applies to the gathered sequence: ``window`` works unchanged, and
+    an explicit ``kv_lo`` must be the FULL-sequence bound ([T_full] or
+    [B, T_full]), not the local shard's."""
+    return _attention(q, k, v, causal=True, window=window, kv_lo=kv_lo)
 
 
 def full_attention(q, k, v) -> torch.Tensor:
