@@ -5,14 +5,26 @@
 // fp32 [T,T] score tensor) with one MFMA kernel using online softmax
 // (O(T) memory) and fp32 accumulation.
 //
-// v1 structure (correctness-first; the 8-wave swapped-QK^T structure of the
-// CDNA4 guide is the optimization target for later passes):
-//   grid  = (T/64, B*H); block = 256 threads = 4 waves
-//   each wave owns 16 q rows; the block shares K/V tiles of 32 keys staged
-//   in LDS; per kv-tile each wave computes S[16][32] with
-//   v_mfma_f32_16x16x32_bf16 (contraction over D in 32-slices), does the
-//   online-softmax update through wave-private LDS, and accumulates
-//   O[16][D] with PV MFMAs.
+// Five kernels, all 256 threads = 4 waves, bh on grid.x (fastest) and the
+// tile index on grid.y, K/V/Q/dO tiles staged in dynamic LDS:
+//   attn_fwd_kernel     v1 forward, 64 q rows per block (16 per wave), kv
+//                       tiles of 32 keys: S[16][32] on 16x16x32 MFMAs,
+//                       online softmax in registers, P through a wave-private
+//                       LDS tile into the PV MFMAs.  Every D; every T % 64.
+//   attn_fwd_v2_kernel  v2 forward, 128 q rows per block (32 per wave):
+//                       swapped QK^T on 32x32x16 MFMAs, lane-local softmax,
+//                       P stays in registers.  T % 128 == 0 and D <= 128.
+//   attn_delta_kernel   delta = rowsum(dO o O), one wave per row.
+//   attn_bwd_kernel     dK/dV: one block per 64 keys loops over q tiles of
+//                       32 rows, recomputes P from the saved LSE and
+//                       accumulates dK/dV in registers.
+//   attn_dq_kernel      dQ: one block per 64 q rows loops over key tiles of
+//                       32 and accumulates dQ in registers (no atomics).
+// The host part at the end of the file picks the instantiations: attn_plan
+// turns (T, D, kv_lo?) and the environment switches into a plan, one
+// selection routine per kernel family maps the plan to a variant (typed
+// kernel + LDS size of its own struct + the arguments its name is printed
+// from), and attn_fwd / attn_bwd / attn_dispatch all go through those.
 //
 // Fragment layouts validated on MI355X hardware (tools/mfma_probe.hip):
 //   A[m][k]: lane l, slot j (0..7) -> A[l&15][(l>>4)*8 + j]
@@ -22,7 +34,10 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <atomic>
+
 #include "common.h"
+#include "ops.h"
 
 namespace samd {
 
@@ -302,7 +317,8 @@ __global__ void attn_fwd_kernel(const unsigned short* __restrict__ Q,
 }
 
 // ===========================================================================
-// Forward v2 (opt-in: SAMD_ATTN_V2=1): the CDNA4-guide structure — swapped
+// Forward v2 (the default where it is built: T % 128 == 0 and D <= 128;
+// SAMD_ATTN_V2=0 takes v1): the CDNA4-guide structure — swapped
 // QK^T on v_mfma_f32_32x32x16_bf16 so each lane's 16 score values belong to
 // ONE q row (lane-local online softmax, one shfl_xor(32) merge), P stays in
 // registers and reaches the PV A-fragment via permlane32_swap half
@@ -469,8 +485,13 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
     // permlane32_swap.  pk[i] packs keys (2i, 2i+1) of this lane's set:
     //   lo half (hi=0): keys {0,1},{2,3},{8,9},{10,11},{16,17},...
     //   hi half (hi=1): keys {4,5},{6,7},{12,13},{14,15},...
-    // after swap(pk[2g], pk[2g+1]? see below) each lane holds the pairs of
-    // ITS A-fragment rows: frag keys (l>>5)*8 + 0..7 per 16-key tile.
+    // The PV A-fragment of a lane holds keys (l>>5)*8 + 0..7 of each 16-key
+    // tile g.  The lo half owns (0,1),(2,3) of those and lacks (4,5),(6,7),
+    // which the hi half holds in pk[4g+0..1]; the hi half owns
+    // (12,13),(14,15) and lacks (8,9),(10,11), which the lo half holds in
+    // pk[4g+2..3].  permlane32_swap(a, b) exchanges a's hi half with b's lo
+    // half, so swap(pk[4g+i], pk[4g+2+i]), i = 0, 1, moves exactly the
+    // lacking pairs and leaves every lane with its own fragment.
     unsigned pk[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -481,7 +502,7 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
     // tile g (g=0: keys 0-15, g=1: keys 16-31): lane pairs pk[4g+0..3] hold
     //   hi=0: (0,1),(2,3),(8,9),(10,11)   [+16 for g=1]
     //   hi=1: (4,5),(6,7),(12,13),(14,15)
-    // swap(pk[4g+0], pk[4g+2]): lo lane gets {(0,1) | (4,5)->? }
+    // swap(pk[4g+0], pk[4g+2]) -> r0, swap(pk[4g+1], pk[4g+3]) -> r1:
     bf16x8 pa[2];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
@@ -516,7 +537,8 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
       for (int dv = 0; dv < D / 32; ++dv) oacc[dv][reg] *= al;
     }
 
-    // ---- PV: O^T? no — O[q][d] += P[q][k] V[k][d]:
+    // ---- PV, not swapped: O[q][d] += P[q][k] V[k][d] keeps q on the MFMA
+    // row dim, so oacc's rows are the q rows the epilogue stores.
     // mfma(A=pa (32 q x 16 k), B=V[k][d] 16x32) per (key half g, dv)
 #pragma unroll
     for (int dv = 0; dv < D / 32; ++dv) {
@@ -558,193 +580,20 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
     LSE[bh * (long)T + q0 + qr] = m_row + __logf(l_row);
 }
 
-
-
-// ---------------------------------------------------------------------------
-// Dispatch rules.  Each environment switch is read once per process; the
-// predicates below are the ONLY place a (T, D) -> kernel decision is made:
-// the launchers and attn_dispatch() (which reports the decision to the
-// tests) both go through them.
-// ---------------------------------------------------------------------------
-static bool env_is(const char* name, char c) {
-  const char* e = getenv(name);
-  return e && e[0] == c;
-}
-// v2 structure (swapped 32x32 MFMAs, in-register P): default ON for the
-// shapes it supports (+40% measured at D=128/64); SAMD_ATTN_V2=0 forces
-// the v1 16x16 structure.
-static bool sw_v2() {
-  static const bool v = !env_is("SAMD_ATTN_V2", '0');
-  return v;
-}
-// default ON for D<=128 (measured +2-11% bwd across shapes);
-// SAMD_ATTN_BWD_TR16=0 reverts to scalar gathers
-static bool sw_tr16() {
-  static const bool v = !env_is("SAMD_ATTN_BWD_TR16", '0');
-  return v;
-}
-static bool sw_dq_gkv() {
-  static const bool v = env_is("SAMD_ATTN_DQ_GKV", '1');
-  return v;
-}
-// V tile from L2 instead of LDS at D<=128 (SAMD_ATTN_BWD_VL2=1): trades
-// per-q-tile L2 re-reads for 62->45 KB LDS/block (3 blocks/CU scalar path)
-static bool sw_vl2() {
-  static const bool v = env_is("SAMD_ATTN_BWD_VL2", '1');
-  return v;
-}
-// D=256 would spill at the v2 structure (256 VGPRs + 53); v1 handles it
-static bool fwd_is_v2(int T, int D) {
-  return sw_v2() && T % 128 == 0 && D <= 128;
-}
-static bool bwd_is_tr16(int D) { return sw_tr16() && D <= 128; }
-static bool bwd_is_vl2(int D) { return sw_vl2() && D <= 128; }
-static bool dq_is_gkv(int D) { return sw_dq_gkv() && D > 128; }
-
-// The kernel instantiations attn_fwd / attn_bwd launch for a padded T and
-// a head size D in this process, space-separated.
-// has_lo: the instantiations taken when a kv_lo bound is given (the names
-// then carry the LO template argument).
-std::string attn_dispatch(int64_t T, int64_t D, bool has_lo) {
-  TORCH_CHECK(T > 0 && T % QBLK == 0, "attn_dispatch: T must be a multiple of 64");
-  TORCH_CHECK(D == 64 || D == 128 || D == 256, "attn_dispatch: D in {64,128,256}");
-  const int t = (int)T, d = (int)D;
-  const std::string ds = std::to_string(d);
-  const bool gkv = dq_is_gkv(d);
-  const char* lo = has_lo ? ",1>" : ">";
-  return std::string(fwd_is_v2(t, d) ? "attn_fwd_v2_kernel<" : "attn_fwd_kernel<") +
-         ds + lo + " attn_delta_kernel<" + ds + "> attn_bwd_kernel<" + ds + "," +
-         (bwd_is_tr16(d) ? "1," : "0,") + (bwd_is_vl2(d) ? "1" : "0") + lo +
-         " attn_dq_kernel<" + ds + "," +
-         (!gkv && bwd_is_tr16(d) ? "1," : "0,") + (gkv ? "1" : "0") + lo;
-}
-
-// kv_lo: optional int32 [B, T] or [T] (batch stride 0) per-row lower key
-// bound, shared by all heads: row t of batch b attends key j iff
-// kv_lo[b,t] <= j <= t and j < kv_len.  The caller guarantees
-// 0 <= kv_lo[b,t] <= t and kv_lo[b,.] non-decreasing (flash.py is the only
-// producer); nothing here reads the values on the host.
-struct LoArg {
-  const int* ptr;
-  long sb;
-};
-static LoArg lo_arg(const c10::optional<at::Tensor>& kv_lo,
-                    const at::Tensor& q, bool causal, const char* who) {
-  if (!kv_lo.has_value()) return LoArg{nullptr, 0};
-  const at::Tensor& lo = *kv_lo;
-  const int64_t B = q.size(0), T = q.size(2);
-  TORCH_CHECK(causal, who, ": kv_lo requires causal=True");
-  TORCH_CHECK(lo.scalar_type() == at::kInt, who, ": kv_lo must be int32");
-  TORCH_CHECK(lo.is_cuda() && lo.device() == q.device(), who,
-              ": kv_lo must be on q's device");
-  TORCH_CHECK((lo.dim() == 1 && lo.size(0) == T) ||
-                  (lo.dim() == 2 && lo.size(0) == B && lo.size(1) == T),
-              who, ": kv_lo must have shape [T] or [B, T] (padded T)");
-  TORCH_CHECK(lo.is_contiguous(), who, ": kv_lo must be contiguous");
-  return LoArg{lo.data_ptr<int>(), lo.dim() == 2 ? (long)T : 0L};
-}
-
-// ---------------------------------------------------------------------------
-// Host wrapper
-// ---------------------------------------------------------------------------
-std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                                 bool causal, int64_t kv_len,
-                                 c10::optional<at::Tensor> kv_lo) {
-  // kv_len < T marks ragged sequences: q/k/v are zero-padded to a 64
-  // multiple by the wrapper and keys >= kv_len are masked out in-kernel
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16,
-              "attn_fwd: bf16 only");
-  TORCH_CHECK(q.dim() == 4, "attn_fwd: [B, H, T, D]");
-  TORCH_CHECK(q.stride(3) == 1 && k.stride(3) == 1 && v.stride(3) == 1,
-              "attn_fwd: innermost dim must be dense");
-  const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2),
-            D = (int)q.size(3);
-  const int Hkv = (int)k.size(1);
-  TORCH_CHECK(H % Hkv == 0, "attn_fwd: q heads must be a multiple of kv heads");
-  TORCH_CHECK(k.size(2) == T, "attn_fwd: q/k length mismatch");
-  TORCH_CHECK(T % QBLK == 0, "attn_fwd: T must be a multiple of 64");
-  if (kv_len <= 0) kv_len = T;
-  TORCH_CHECK(kv_len <= T, "attn_fwd: kv_len exceeds padded T");
-  TORCH_CHECK(D == 64 || D == 128 || D == 256, "attn_fwd: D in {64,128,256}");
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(q.data_ptr()) & 15) == 0 &&
-              q.stride(2) % 8 == 0 && k.stride(2) % 8 == 0 &&
-              v.stride(2) % 8 == 0, "attn_fwd: rows must be 16-B aligned");
-  const LoArg lo = lo_arg(kv_lo, q, causal, "attn_fwd");
-
-  // output physically [B, T, H, D]: the model's post-attention
-  // transpose(1,2).reshape is then a zero-copy view
-  auto o_phys = at::empty({B, T, H, D}, q.options());
-  auto o = o_phys.permute({0, 2, 1, 3});
-  auto lse = at::empty({B, H, T}, q.options().dtype(at::kFloat));
-  auto stream = at::hip::getCurrentHIPStream();
-  const float scale = 1.f / sqrtf((float)D);
-
-  if (fwd_is_v2(T, D)) {
-    dim3 grid2(B * H, T / 128), block2(256);
-#define LAUNCH_V2(DD, LO)                                                    \
-    do {                                                                     \
-      size_t shmem = sizeof(AttnV2Lds<DD>);                                  \
-      hipLaunchKernelGGL((attn_fwd_v2_kernel<DD, LO>), grid2, block2, shmem, \
-                         stream.stream(),                                    \
-                         reinterpret_cast<const unsigned short*>(q.data_ptr()), \
-                         reinterpret_cast<const unsigned short*>(k.data_ptr()), \
-                         reinterpret_cast<const unsigned short*>(v.data_ptr()), \
-                         reinterpret_cast<unsigned short*>(o.data_ptr()),    \
-                         lse.data_ptr<float>(), T, H, Hkv, scale,            \
-                         causal ? 1 : 0, (int)kv_len, str_of(q), str_of(k),  \
-                         str_of(v), str_of(o), lo.ptr, lo.sb);               \
-    } while (0)
-    if (lo.ptr) {
-      if (D == 64) LAUNCH_V2(64, true);
-      else LAUNCH_V2(128, true);
-    } else {
-      if (D == 64) LAUNCH_V2(64, false);
-      else LAUNCH_V2(128, false);
-    }
-#undef LAUNCH_V2
-    return {o, lse};
-  }
-  dim3 grid(B * H, T / QBLK), block(256);
-
-#define LAUNCH(DD, LO)                                                      \
-  do {                                                                      \
-    size_t shmem = sizeof(AttnLds<DD>);                                     \
-    hipLaunchKernelGGL((attn_fwd_kernel<DD, LO>), grid, block, shmem,       \
-                       stream.stream(),                                     \
-                       reinterpret_cast<const unsigned short*>(q.data_ptr()), \
-                       reinterpret_cast<const unsigned short*>(k.data_ptr()), \
-                       reinterpret_cast<const unsigned short*>(v.data_ptr()), \
-                       reinterpret_cast<unsigned short*>(o.data_ptr()),     \
-                       lse.data_ptr<float>(), T, H, Hkv, scale,             \
-                       causal ? 1 : 0, (int)kv_len, str_of(q), str_of(k),   \
-                       str_of(v), str_of(o), lo.ptr, lo.sb);                \
-  } while (0)
-
-  if (lo.ptr) {
-    if (D == 64) LAUNCH(64, true);
-    else if (D == 128) LAUNCH(128, true);
-    else LAUNCH(256, true);
-  } else {
-    if (D == 64) LAUNCH(64, false);
-    else if (D == 128) LAUNCH(128, false);
-    else LAUNCH(256, false);
-  }
-#undef LAUNCH
-  return {o, lse};
-}
-
-}  // namespace samd
-
 // ===========================================================================
-// Backward (FA2 scheme): grid over kv tiles; each block owns 64 keys
-// (16 per wave) and loops over q tiles of 32 rows, recomputing P from the
-// saved LSE.  dK/dV accumulate in registers across the q loop; dQ partials
-// go to a fp32 buffer with atomics (summed across kv blocks).
+// Backward (FA2 scheme), three kernels, P recomputed from the saved LSE:
+//   attn_delta_kernel  delta = rowsum(dO o O).
+//   attn_bwd_kernel    dK/dV.  Grid over kv tiles: each block owns 64 keys
+//                      (16 per wave), loops over q tiles of 32 rows and
+//                      accumulates dK/dV in registers across the loop; stored
+//                      once as bf16, or added to fp32 buffers with atomics
+//                      when several q heads share a kv head (GQA).
+//   attn_dq_kernel     dQ.  Grid over q blocks: each block owns 64 q rows,
+//                      loops over key tiles of 32 and accumulates dQ in
+//                      registers; stored once as bf16, no atomics.
 //   dV = P^T dO;  dP^T = V dO^T;  dS^T = P^T o (dP^T - delta) * scale;
-//   dK = dS^T Q;  dQ = dS K;  delta = rowsum(dO o O) (computed by caller).
+//   dK = dS^T Q;  dQ = dS K.
 // ===========================================================================
-
-namespace samd {
 
 namespace bwd {
 constexpr int KB = 64;   // keys per block
@@ -1248,27 +1097,56 @@ __global__ void attn_dq_kernel(const unsigned short* __restrict__ dO,
   }
 }
 
-std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
-                                 at::Tensor v, at::Tensor o, at::Tensor lse,
-                                 bool causal, int64_t kv_len,
-                                 c10::optional<at::Tensor> kv_lo) {
-  using namespace bwd;
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16);
-  const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2),
-            D = (int)q.size(3);
-  const int Hkv = (int)k.size(1);
-  TORCH_CHECK(H % Hkv == 0);
-  TORCH_CHECK(T % KB == 0, "attn_bwd: T must be a multiple of 64");
-  if (kv_len <= 0) kv_len = T;
-  TORCH_CHECK(kv_len <= T, "attn_bwd: kv_len exceeds padded T");
-  TORCH_CHECK(D == 64 || D == 128 || D == 256);
-  TORCH_CHECK(dout.stride(3) == 1 && q.stride(3) == 1 && k.stride(3) == 1 &&
-              v.stride(3) == 1, "attn_bwd: innermost dim must be dense");
-  TORCH_CHECK(dout.stride(2) % 8 == 0 && q.stride(2) % 8 == 0 &&
-              k.stride(2) % 8 == 0 && v.stride(2) % 8 == 0);
-  const LoArg lo = lo_arg(kv_lo, q, causal, "attn_bwd");
-  if (lo.ptr) {
-    // the kv_lo instantiations exist for the default dispatch only
+// ===========================================================================
+// Host part: plan -> variant -> launch.
+// ===========================================================================
+
+// Environment switches, each read once per process.
+static bool env_is(const char* name, char c) {
+  const char* e = getenv(name);
+  return e && e[0] == c;
+}
+// v2 structure (swapped 32x32 MFMAs, in-register P): default ON for the
+// shapes it supports (+40% measured at D=128/64); SAMD_ATTN_V2=0 forces
+// the v1 16x16 structure.
+static bool sw_v2() {
+  static const bool v = !env_is("SAMD_ATTN_V2", '0');
+  return v;
+}
+// default ON for D<=128 (measured +2-11% bwd across shapes);
+// SAMD_ATTN_BWD_TR16=0 reverts to scalar gathers
+static bool sw_tr16() {
+  static const bool v = !env_is("SAMD_ATTN_BWD_TR16", '0');
+  return v;
+}
+// GKV (K/V/Q/dO fragments from L2, 17 KB LDS, 3 blocks/CU) measured SLOWER
+// at D=256 (612 vs 525 us at the GPT-J bench shape: the L2 re-reads cost
+// more than the occupancy gains) — kept as an opt-in probe only
+static bool sw_dq_gkv() {
+  static const bool v = env_is("SAMD_ATTN_DQ_GKV", '1');
+  return v;
+}
+// V tile from L2 instead of LDS at D<=128 (SAMD_ATTN_BWD_VL2=1): trades
+// per-q-tile L2 re-reads for 62->45 KB LDS/block (3 blocks/CU scalar path)
+static bool sw_vl2() {
+  static const bool v = env_is("SAMD_ATTN_BWD_VL2", '1');
+  return v;
+}
+
+// The (T, D, kv_lo?) -> kernel decision.  attn_plan is the only reader of the
+// switches; the selection routines below turn a plan into instantiations.
+struct AttnPlan {
+  bool fwd_v2;  // v2 forward (D=256 would spill there: 256 VGPRs + 53)
+  bool tr16;    // dK/dV and dQ: tr16 B-fragment reads
+  bool vl2;     // dK/dV: V from L2
+  bool gkv;     // dQ: K/V/Q/dO fragments from L2
+  bool lo;      // the kv_lo instantiations
+};
+// bwd: the plan will select backward kernels (attn_bwd, attn_dispatch).  The
+// kv_lo backward is built for the default switches only and refused by name
+// otherwise; the kv_lo forward is built for every setting.
+static AttnPlan attn_plan(int T, int D, bool has_lo, bool bwd = true) {
+  if (has_lo && bwd) {
     TORCH_CHECK(sw_tr16(), "attn_bwd: kv_lo is not built for "
                 "SAMD_ATTN_BWD_TR16=0; unset the switch");
     TORCH_CHECK(!sw_vl2(), "attn_bwd: kv_lo is not built for "
@@ -1276,6 +1154,259 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
     TORCH_CHECK(!sw_dq_gkv(), "attn_bwd: kv_lo is not built for "
                 "SAMD_ATTN_DQ_GKV=1; unset the switch");
   }
+  return AttnPlan{sw_v2() && T % 128 == 0 && D <= 128, sw_tr16() && D <= 128,
+                  sw_vl2() && D <= 128, sw_dq_gkv() && D > 128, has_lo};
+}
+
+// One launched instantiation.  Everything here comes from the template
+// arguments of the *_of() function that made it, so the kernel, its LDS size
+// and its reported name cannot disagree.
+template <class Fn>
+struct Variant {
+  Fn* kernel;
+  int lds;           // sizeof the struct this kernel lays over its dynamic LDS
+  int rows;          // q rows (keys for dK/dV) per block: grid.y = T / rows
+  // MaxDynamicSharedMemorySize set for this instantiation?  nullptr: never
+  // needed (forward and delta, < 64 KB)
+  std::atomic<bool>* lds_raised;
+  const char* stem;  // reported as stem<args...>, then ",1" for LO
+  int nargs, args[3];
+  bool lo;
+};
+using FwdVariant = Variant<decltype(attn_fwd_kernel<64, false>)>;
+using DeltaVariant = Variant<decltype(attn_delta_kernel<64>)>;
+using BwdVariant = Variant<decltype(attn_bwd_kernel<64, false, false, false>)>;
+using DqVariant = Variant<decltype(attn_dq_kernel<64, false, false, false>)>;
+
+template <int D, bool LO>
+static FwdVariant fwd_v1_of() {
+  return {&attn_fwd_kernel<D, LO>, (int)sizeof(AttnLds<D>), QBLK, nullptr,
+          "attn_fwd_kernel", 1, {D}, LO};
+}
+template <int D, bool LO>
+static FwdVariant fwd_v2_of() {
+  return {&attn_fwd_v2_kernel<D, LO>, (int)sizeof(AttnV2Lds<D>), 4 * 32,
+          nullptr, "attn_fwd_v2_kernel", 1, {D}, LO};
+}
+template <int D>
+static DeltaVariant delta_of() {
+  return {&attn_delta_kernel<D>, 0, 4, nullptr, "attn_delta_kernel", 1, {D},
+          false};
+}
+template <int D, bool TR16, bool VL2, bool LO>
+static BwdVariant bwd_of() {
+  static std::atomic<bool> raised{false};
+  constexpr bool HASV = (D <= 128) && !VL2;  // as in the kernel
+  return {&attn_bwd_kernel<D, TR16, VL2, LO>,
+          (int)sizeof(AttnBwdLdsT<D, HASV, LO>), bwd::KB, &raised,
+          "attn_bwd_kernel", 3, {D, TR16, VL2}, LO};
+}
+template <int D, bool TR16, bool GKV, bool LO>
+static DqVariant dq_of() {
+  static std::atomic<bool> raised{false};
+  return {&attn_dq_kernel<D, TR16, GKV, LO>, (int)sizeof(AttnDqLds<D, GKV>),
+          dq::QB, &raised, "attn_dq_kernel", 3, {D, TR16, GKV}, LO};
+}
+
+// f(D as a compile-time constant); D is one of 64, 128, 256 by now.
+template <class F>
+static auto with_d(int D, F f) {
+  if (D == 64) return f(std::integral_constant<int, 64>{});
+  if (D == 128) return f(std::integral_constant<int, 128>{});
+  return f(std::integral_constant<int, 256>{});
+}
+
+// Plan -> variant, one routine per kernel family.  What these can return is
+// the whole set of instantiations in the extension.
+static FwdVariant fwd_variant(const AttnPlan& p, int D) {
+  return with_d(D, [&](auto d) -> FwdVariant {
+    constexpr int DD = decltype(d)::value;
+    if constexpr (DD <= 128) {
+      if (p.fwd_v2) return p.lo ? fwd_v2_of<DD, true>() : fwd_v2_of<DD, false>();
+    }
+    return p.lo ? fwd_v1_of<DD, true>() : fwd_v1_of<DD, false>();
+  });
+}
+static DeltaVariant delta_variant(int D) {
+  return with_d(D, [](auto d) { return delta_of<decltype(d)::value>(); });
+}
+static BwdVariant bwd_variant(const AttnPlan& p, int D) {
+  return with_d(D, [&](auto d) -> BwdVariant {
+    constexpr int DD = decltype(d)::value;
+    if (p.lo) return bwd_of<DD, (DD <= 128), false, true>();
+    if constexpr (DD <= 128) {
+      if (p.tr16)
+        return p.vl2 ? bwd_of<DD, true, true, false>()
+                     : bwd_of<DD, true, false, false>();
+      if (p.vl2) return bwd_of<DD, false, true, false>();
+    }
+    return bwd_of<DD, false, false, false>();
+  });
+}
+static DqVariant dq_variant(const AttnPlan& p, int D) {
+  return with_d(D, [&](auto d) -> DqVariant {
+    constexpr int DD = decltype(d)::value;
+    if (p.lo) return dq_of<DD, (DD <= 128), false, true>();
+    if constexpr (DD <= 128) {
+      if (p.tr16) return dq_of<DD, true, false, false>();
+    } else {
+      if (p.gkv) return dq_of<DD, false, true, false>();
+    }
+    return dq_of<DD, false, false, false>();
+  });
+}
+
+template <class Fn>
+static std::string name_of(const Variant<Fn>& v) {
+  std::string s = std::string(v.stem) + "<" + std::to_string(v.args[0]);
+  for (int i = 1; i < v.nargs; ++i) s += "," + std::to_string(v.args[i]);
+  return s + (v.lo ? ",1>" : ">");
+}
+
+// The kernel instantiations attn_fwd / attn_bwd launch for a padded T and
+// a head size D in this process, space-separated.
+// has_lo: the instantiations taken when a kv_lo bound is given (the names
+// then carry the LO template argument).
+std::string attn_dispatch(int64_t T, int64_t D, bool has_lo) {
+  TORCH_CHECK(T > 0 && T % QBLK == 0, "attn_dispatch: T must be a multiple of 64");
+  TORCH_CHECK(D == 64 || D == 128 || D == 256, "attn_dispatch: D in {64,128,256}");
+  const int d = (int)D;
+  const AttnPlan p = attn_plan((int)T, d, has_lo);
+  return name_of(fwd_variant(p, d)) + " " + name_of(delta_variant(d)) + " " +
+         name_of(bwd_variant(p, d)) + " " + name_of(dq_variant(p, d));
+}
+
+// Typed launch at 256 threads with the variant's own LDS size; a variant
+// that can need more than the default LDS limit has the limit raised first,
+// once per process.
+template <class Fn, class... Args>
+static void launch(const Variant<Fn>& v, dim3 grid, hipStream_t stream,
+                   Args... args) {
+  if (v.lds_raised && !v.lds_raised->load(std::memory_order_relaxed)) {
+    SAMD_CHECK_HIP(hipFuncSetAttribute(
+        reinterpret_cast<const void*>(v.kernel),
+        hipFuncAttributeMaxDynamicSharedMemorySize, v.lds));
+    v.lds_raised->store(true, std::memory_order_relaxed);
+  }
+  hipLaunchKernelGGL(v.kernel, grid, dim3(256), v.lds, stream, args...);
+  SAMD_CHECK_HIP(hipGetLastError());
+}
+
+static const unsigned short* bf16_in(const at::Tensor& t) {
+  return reinterpret_cast<const unsigned short*>(t.data_ptr());
+}
+static unsigned short* bf16_out(const at::Tensor& t) {
+  return reinterpret_cast<unsigned short*>(t.data_ptr());
+}
+
+// kv_lo: optional int32 [B, T] or [T] (batch stride 0) per-row lower key
+// bound, shared by all heads: row t of batch b attends key j iff
+// kv_lo[b,t] <= j <= t and j < kv_len.  The caller guarantees
+// 0 <= kv_lo[b,t] <= t and kv_lo[b,.] non-decreasing (flash.py is the only
+// producer); nothing here reads the values on the host.
+struct LoArg {
+  const int* ptr;
+  long sb;
+};
+static LoArg lo_arg(const c10::optional<at::Tensor>& kv_lo,
+                    const at::Tensor& q, bool causal, const char* who) {
+  if (!kv_lo.has_value()) return LoArg{nullptr, 0};
+  const at::Tensor& lo = *kv_lo;
+  const int64_t B = q.size(0), T = q.size(2);
+  TORCH_CHECK(causal, who, ": kv_lo requires causal=True");
+  TORCH_CHECK(lo.scalar_type() == at::kInt, who, ": kv_lo must be int32");
+  TORCH_CHECK(lo.is_cuda() && lo.device() == q.device(), who,
+              ": kv_lo must be on q's device");
+  TORCH_CHECK((lo.dim() == 1 && lo.size(0) == T) ||
+                  (lo.dim() == 2 && lo.size(0) == B && lo.size(1) == T),
+              who, ": kv_lo must have shape [T] or [B, T] (padded T)");
+  TORCH_CHECK(lo.is_contiguous(), who, ": kv_lo must be contiguous");
+  return LoArg{lo.data_ptr<int>(), lo.dim() == 2 ? (long)T : 0L};
+}
+
+// The q/k/v checks of both entry points (who: "attn_fwd" / "attn_bwd").
+// kv_len < T marks ragged sequences: q/k/v are zero-padded to a 64 multiple
+// by the wrapper and keys >= kv_len are masked out in-kernel; kv_len <= 0
+// means T.  Only q's pointer is held to 16 B: rows of k and v that start 8 B
+// off work on this hardware and stay accepted.
+struct AttnDims {
+  int B, H, Hkv, T, D;
+};
+static bool bf16_on(const at::Tensor& t, const at::Tensor& q) {
+  return t.scalar_type() == at::kBFloat16 && t.device() == q.device();
+}
+static AttnDims check_qkv(const at::Tensor& q, const at::Tensor& k,
+                          const at::Tensor& v, int64_t& kv_len,
+                          const char* who) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, who,
+              ": bf16 only");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, who,
+              ": [B, H, T, D]");
+  TORCH_CHECK(q.stride(3) == 1 && k.stride(3) == 1 && v.stride(3) == 1, who,
+              ": innermost dim must be dense");
+  const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2),
+            D = (int)q.size(3);
+  const int Hkv = (int)k.size(1);
+  TORCH_CHECK(Hkv > 0 && H % Hkv == 0, who,
+              ": q heads must be a multiple of kv heads");
+  TORCH_CHECK(k.size(2) == T, who, ": q/k length mismatch");
+  TORCH_CHECK(T % QBLK == 0, who, ": T must be a multiple of 64");
+  if (kv_len <= 0) kv_len = T;
+  TORCH_CHECK(kv_len <= T, who, ": kv_len exceeds padded T");
+  TORCH_CHECK(D == 64 || D == 128 || D == 256, who, ": D in {64,128,256}");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(q.data_ptr()) & 15) == 0 &&
+              q.stride(2) % 8 == 0 && k.stride(2) % 8 == 0 &&
+              v.stride(2) % 8 == 0, who, ": rows must be 16-B aligned");
+  TORCH_CHECK(bf16_on(k, q), who, ": k must be bf16 on q's device");
+  TORCH_CHECK(bf16_on(v, q), who, ": v must be bf16 on q's device");
+  TORCH_CHECK(k.size(0) == B && k.size(3) == D, who,
+              ": k must be [B, Hkv, T, D] with q's B, T and D");
+  TORCH_CHECK(v.sizes() == k.sizes(), who, ": v must have k's sizes");
+  return AttnDims{B, H, Hkv, T, D};
+}
+
+std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
+                                 bool causal, int64_t kv_len,
+                                 c10::optional<at::Tensor> kv_lo) {
+  const auto [B, H, Hkv, T, D] = check_qkv(q, k, v, kv_len, "attn_fwd");
+  const LoArg lo = lo_arg(kv_lo, q, causal, "attn_fwd");
+
+  // output physically [B, T, H, D]: the model's post-attention
+  // transpose(1,2).reshape is then a zero-copy view
+  auto o_phys = at::empty({B, T, H, D}, q.options());
+  auto o = o_phys.permute({0, 2, 1, 3});
+  auto lse = at::empty({B, H, T}, q.options().dtype(at::kFloat));
+  const float scale = 1.f / sqrtf((float)D);
+
+  const FwdVariant fv =
+      fwd_variant(attn_plan(T, D, lo.ptr != nullptr, /*bwd=*/false), D);
+  launch(fv, dim3(B * H, T / fv.rows), at::hip::getCurrentHIPStream().stream(),
+         bf16_in(q), bf16_in(k), bf16_in(v), bf16_out(o),
+         lse.data_ptr<float>(), T, H, Hkv, scale, causal ? 1 : 0, (int)kv_len,
+         str_of(q), str_of(k), str_of(v), str_of(o), lo.ptr, lo.sb);
+  return {o, lse};
+}
+
+std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
+                                 at::Tensor v, at::Tensor o, at::Tensor lse,
+                                 bool causal, int64_t kv_len,
+                                 c10::optional<at::Tensor> kv_lo) {
+  const auto [B, H, Hkv, T, D] = check_qkv(q, k, v, kv_len, "attn_bwd");
+  TORCH_CHECK(dout.sizes() == q.sizes(), "attn_bwd: dout must have q's sizes");
+  TORCH_CHECK(o.sizes() == q.sizes(), "attn_bwd: o must have q's sizes");
+  TORCH_CHECK(bf16_on(dout, q), "attn_bwd: dout must be bf16 on q's device");
+  TORCH_CHECK(bf16_on(o, q), "attn_bwd: o must be bf16 on q's device");
+  TORCH_CHECK(dout.stride(3) == 1, "attn_bwd: dout innermost dim must be dense");
+  TORCH_CHECK(o.stride(3) == 1, "attn_bwd: o innermost dim must be dense");
+  TORCH_CHECK(dout.stride(2) % 8 == 0, "attn_bwd: dout rows must be 16-B aligned");
+  // the kernels index lse and delta as bh * T + t
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.device() == q.device(),
+              "attn_bwd: lse must be fp32 on q's device");
+  TORCH_CHECK(lse.dim() == 3 && lse.size(0) == B && lse.size(1) == H &&
+                  lse.size(2) == T && lse.is_contiguous(),
+              "attn_bwd: lse must be a contiguous [B, H, T] tensor");
+  const LoArg lo = lo_arg(kv_lo, q, causal, "attn_bwd");
+  const AttnPlan plan = attn_plan(T, D, lo.ptr != nullptr);
 
   auto delta = at::empty({B, H, T}, q.options().dtype(at::kFloat));
   // grads physically [B, T, H, D] (matches the projection layout upstream,
@@ -1292,142 +1423,28 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
     dv_f32 = at::zeros({B, T, Hkv, D}, q.options().dtype(at::kFloat))
                  .permute({0, 2, 1, 3});
   }
-  auto stream = at::hip::getCurrentHIPStream();
+  hipStream_t stream = at::hip::getCurrentHIPStream().stream();
   const float scale = 1.f / sqrtf((float)D);
-  dim3 grid(B * H, T / KB), block(256);
-  // kernel variants: see the dispatch rules above attn_fwd (numerics of
-  // every switch setting are checked by tests/test_attention_gpu.py)
+  const int c = causal ? 1 : 0, kvl = (int)kv_len;
 
-#define BWD_ARGS                                                             \
-    stream.stream(),                                                         \
-    reinterpret_cast<const unsigned short*>(dout.data_ptr()),                \
-    reinterpret_cast<const unsigned short*>(q.data_ptr()),                   \
-    reinterpret_cast<const unsigned short*>(k.data_ptr()),                   \
-    reinterpret_cast<const unsigned short*>(v.data_ptr()),                   \
-    lse.data_ptr<float>(), delta.data_ptr<float>(),                          \
-    reinterpret_cast<unsigned short*>(dk.data_ptr()),                        \
-    reinterpret_cast<unsigned short*>(dv.data_ptr()),                        \
-    gqa ? dk_f32.data_ptr<float>() : nullptr,                                \
-    gqa ? dv_f32.data_ptr<float>() : nullptr, T, H, Hkv,                     \
-    scale, causal ? 1 : 0, (int)kv_len, str_of(dout), str_of(q),             \
-    str_of(k), str_of(v),                                                    \
-    gqa ? str_of(dk_f32) : str_of(dk),                                       \
-    gqa ? str_of(dv_f32) : str_of(dv), lo.ptr, lo.sb
-
-#define DQ_ARGS                                                              \
-    stream.stream(),                                                         \
-    reinterpret_cast<const unsigned short*>(dout.data_ptr()),                \
-    reinterpret_cast<const unsigned short*>(q.data_ptr()),                   \
-    reinterpret_cast<const unsigned short*>(k.data_ptr()),                   \
-    reinterpret_cast<const unsigned short*>(v.data_ptr()),                   \
-    lse.data_ptr<float>(), delta.data_ptr<float>(),                          \
-    reinterpret_cast<unsigned short*>(dq.data_ptr()),                        \
-    T, H, Hkv, scale, causal ? 1 : 0, (int)kv_len,                           \
-    str_of(dout), str_of(q), str_of(k), str_of(v), str_of(dq), lo.ptr, lo.sb
-
-#define LAUNCH_B(DD)                                                         \
-  do {                                                                       \
-    dim3 dgrid(std::min((T + 3) / 4, 2048), B * H), dblock(256);             \
-    hipLaunchKernelGGL((attn_delta_kernel<DD>), dgrid, dblock, 0,            \
-                       stream.stream(),                                      \
-                       reinterpret_cast<const unsigned short*>(dout.data_ptr()), \
-                       reinterpret_cast<const unsigned short*>(o.data_ptr()), \
-                       delta.data_ptr<float>(), T, H, str_of(dout),          \
-                       str_of(o));                                           \
-    /* GKV (K/V/Q/dO fragments from L2, 17 KB LDS, 3 blocks/CU) measured \
-       SLOWER at D=256 (612 vs 525 us at the GPT-J bench shape: the L2   \
-       re-reads cost more than the occupancy gains) — kept as an opt-in  \
-       probe only */                                                       \
-    const bool gkv = dq_is_gkv(DD);                                          \
-    size_t SH_DQ = gkv ? sizeof(AttnDqLds<DD, true>)                         \
-                       : sizeof(AttnDqLds<DD, false>);                       \
-    static bool dq_attr_##DD = [] {                                          \
-      hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(                                     \
-              &attn_dq_kernel<DD, false, false, false>),                     \
-          hipFuncAttributeMaxDynamicSharedMemorySize,                        \
-          (int)sizeof(AttnDqLds<DD, false>));                                \
-      hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(                                     \
-              &attn_dq_kernel<DD, true, false, false>),                      \
-          hipFuncAttributeMaxDynamicSharedMemorySize,                        \
-          (int)sizeof(AttnDqLds<DD, false>));                                \
-      hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(                                     \
-              &attn_dq_kernel<DD, (DD <= 128), false, true>),                \
-          hipFuncAttributeMaxDynamicSharedMemorySize,                        \
-          (int)sizeof(AttnDqLds<DD, false>));                                \
-      return true;                                                           \
-    }();                                                                     \
-    (void)dq_attr_##DD;                                                      \
-    {                                                                        \
-      dim3 qgrid(B * H, T / dq::QB), qblock(256);                            \
-      if (lo.ptr)                                                            \
-        hipLaunchKernelGGL((attn_dq_kernel<DD, (DD <= 128), false, true>),   \
-                           qgrid, qblock, SH_DQ, DQ_ARGS);                   \
-      else if (gkv)                                                          \
-        hipLaunchKernelGGL((attn_dq_kernel<DD, false, true, false>), qgrid,  \
-                           qblock, SH_DQ, DQ_ARGS);                          \
-      else if (bwd_is_tr16(DD))                                              \
-        hipLaunchKernelGGL((attn_dq_kernel<DD, true, false, false>), qgrid,  \
-                           qblock, SH_DQ, DQ_ARGS);                          \
-      else                                                                   \
-        hipLaunchKernelGGL((attn_dq_kernel<DD, false, false, false>), qgrid, \
-                           qblock, SH_DQ, DQ_ARGS);                          \
-    }                                                                        \
-    const bool tr = bwd_is_tr16(DD);                                         \
-    const bool vl2 = bwd_is_vl2(DD);                                         \
-    constexpr size_t SH_V = sizeof(AttnBwdLds<DD, (DD <= 128)>);             \
-    constexpr size_t SH_N = sizeof(AttnBwdLds<DD, false>);                   \
-    constexpr size_t SH_LO = sizeof(AttnBwdLdsLo<DD, (DD <= 128)>);          \
-    size_t shmem = lo.ptr ? SH_LO : (vl2 ? SH_N : SH_V);                     \
-    static bool attr_set_##DD = [] {                                         \
-      hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(                                     \
-              &attn_bwd_kernel<DD, false, false, false>),                    \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_V);            \
-      hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(                                     \
-              &attn_bwd_kernel<DD, true, false, false>),                     \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_V);            \
-      hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(                                     \
-              &attn_bwd_kernel<DD, false, true, false>),                     \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_N);            \
-      hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(                                     \
-              &attn_bwd_kernel<DD, true, true, false>),                      \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_N);            \
-      hipFuncSetAttribute(                                                   \
-          reinterpret_cast<const void*>(                                     \
-              &attn_bwd_kernel<DD, (DD <= 128), false, true>),               \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_LO);           \
-      return true;                                                           \
-    }();                                                                     \
-    (void)attr_set_##DD;                                                     \
-    if (lo.ptr)                                                              \
-      hipLaunchKernelGGL((attn_bwd_kernel<DD, (DD <= 128), false, true>),    \
-                         grid, block, shmem, BWD_ARGS);                      \
-    else if (tr && vl2)                                                      \
-      hipLaunchKernelGGL((attn_bwd_kernel<DD, true, true, false>), grid,     \
-                         block, shmem, BWD_ARGS);                            \
-    else if (tr)                                                             \
-      hipLaunchKernelGGL((attn_bwd_kernel<DD, true, false, false>), grid,    \
-                         block, shmem, BWD_ARGS);                            \
-    else if (vl2)                                                            \
-      hipLaunchKernelGGL((attn_bwd_kernel<DD, false, true, false>), grid,    \
-                         block, shmem, BWD_ARGS);                            \
-    else                                                                     \
-      hipLaunchKernelGGL((attn_bwd_kernel<DD, false, false, false>), grid,   \
-                         block, shmem, BWD_ARGS);                            \
-  } while (0)
-
-  if (D == 64) LAUNCH_B(64);
-  else if (D == 128) LAUNCH_B(128);
-  else LAUNCH_B(256);
-#undef LAUNCH_B
-#undef DQ_ARGS
-#undef BWD_ARGS
+  launch(delta_variant(D), dim3(std::min((T + 3) / 4, 2048), B * H), stream,
+         bf16_in(dout), bf16_in(o), delta.data_ptr<float>(), T, H,
+         str_of(dout), str_of(o));
+  const DqVariant qv = dq_variant(plan, D);
+  launch(qv, dim3(B * H, T / qv.rows), stream, bf16_in(dout), bf16_in(q),
+         bf16_in(k), bf16_in(v), lse.data_ptr<float>(),
+         delta.data_ptr<float>(), bf16_out(dq), T, H, Hkv, scale, c, kvl,
+         str_of(dout), str_of(q), str_of(k), str_of(v), str_of(dq), lo.ptr,
+         lo.sb);
+  const BwdVariant bv = bwd_variant(plan, D);
+  launch(bv, dim3(B * H, T / bv.rows), stream, bf16_in(dout), bf16_in(q),
+         bf16_in(k), bf16_in(v), lse.data_ptr<float>(),
+         delta.data_ptr<float>(), bf16_out(dk), bf16_out(dv),
+         gqa ? dk_f32.data_ptr<float>() : nullptr,
+         gqa ? dv_f32.data_ptr<float>() : nullptr, T, H, Hkv, scale, c, kvl,
+         str_of(dout), str_of(q), str_of(k), str_of(v),
+         gqa ? str_of(dk_f32) : str_of(dk), gqa ? str_of(dv_f32) : str_of(dv),
+         lo.ptr, lo.sb);
   if (gqa) return {dq, dk_f32.to(at::kBFloat16), dv_f32.to(at::kBFloat16)};
   return {dq, dk, dv};
 }

@@ -10,6 +10,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "ops.h"
 
 namespace samd {
 

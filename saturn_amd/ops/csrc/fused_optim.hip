@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "common.h"
+#include "ops.h"
 
 namespace samd {
 

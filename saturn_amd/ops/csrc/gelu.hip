@@ -13,6 +13,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "ops.h"
 #include "gelu_math.h"  // gelu_f / dgelu_f, shared with mlp_bwd.hip
 
 namespace samd {

@@ -27,20 +27,10 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "ops.h"
 #include "tile_image.h"
 
 namespace samd {
-
-// attention.hip / mlp_bwd.hip
-std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
-                                 at::Tensor v, at::Tensor o, at::Tensor lse,
-                                 bool causal, int64_t kv_len,
-                                 c10::optional<at::Tensor> kv_lo);
-std::vector<at::Tensor> mlp_act_bwd(at::Tensor d_act, at::Tensor pre,
-                                    bool want_dT, bool want_aT);
-// rope.hip
-void rope_apply(at::Tensor y, at::Tensor x, at::Tensor cos_t, at::Tensor sin_t,
-                int64_t t_len, int64_t t_off, bool half_style, bool backward);
 
 namespace {
 

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "common.h"
+#include "ops.h"
 
 namespace samd {
 

@@ -19,6 +19,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "ops.h"
 
 namespace samd {
 

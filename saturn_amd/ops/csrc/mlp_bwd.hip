@@ -32,6 +32,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "ops.h"
 #include "gelu_math.h"
 #include "tile_image.h"
 

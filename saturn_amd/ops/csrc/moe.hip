@@ -26,6 +26,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "ops.h"
 
 namespace samd {
 

@@ -1,10 +1,10 @@
 """Flash attention dispatch (K2).
 
 ``saturn_amd._C.attn_fwd/attn_bwd`` are the hand-written CDNA4 MFMA kernels
-(attention.hip).  Until they are built into the extension, the GPU path
-falls back to the explicit-GEMM math composition (rocBLAS GEMMs + softmax —
-no Triton, no aotriton) and WARNS once: measurements taken on the fallback
-are not this framework's attention numbers.
+(attention.hip); they take bf16 with a head size of 64, 128 or 256.  Any
+other (dtype, head size) goes to the explicit-GEMM math composition (rocBLAS
+GEMMs + softmax — no Triton, no aotriton) and WARNS once with the reason:
+measurements taken on that path are not this framework's attention numbers.
 
 Causal attention takes an optional per-row lower key bound ``kv_lo``: row
 ``t`` of batch ``b`` attends key ``j`` iff ``kv_lo[b, t] <= j <= t``.  A
@@ -130,34 +130,12 @@ class _FlashFn(torch.autograd.Function):
         q, k, v, o, lse = ctx.saved_tensors
         ext = require_ext()
         T = ctx.t_real
-        if hasattr(ext, "attn_bwd"):
-            do = _pad_t64(_dense_rows(do)) if T % 64 else _dense_rows(do)
-            dq, dk, dv = ext.attn_bwd(do, q, k, v, o, lse, ctx.causal, T,
-                                      kv_lo=ctx.kv_lo)
-            if T % 64:
-                dq, dk, dv = dq[:, :, :T], dk[:, :, :T], dv[:, :, :T]
-            return dq, dk, dv, None, None
-        # Analytic FA2 backward composed from rocBLAS GEMMs (recompute P
-        # from the saved LSE; O(T^2) transient, fp32 math).  The fused HIP
-        # backward kernel replaces this path when built.
-        scale = 1.0 / (q.shape[-1] ** 0.5)
-        qf, kf, vf = q.float(), k.float(), v.float()
-        dof, of = do.float(), o.float()
-        s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
-        if ctx.causal:
-            T = q.shape[-2]
-            mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
-            if ctx.kv_lo is not None:
-                mask = mask & lo_mask(ctx.kv_lo)
-            s = s.masked_fill(~mask, float("-inf"))
-        p = torch.exp(s - lse.unsqueeze(-1))
-        dv = torch.matmul(p.transpose(-1, -2), dof)
-        dp = torch.matmul(dof, vf.transpose(-1, -2))
-        delta = (dof * of).sum(-1, keepdim=True)
-        ds = p * (dp - delta) * scale
-        dq = torch.matmul(ds, kf)
-        dk = torch.matmul(ds.transpose(-1, -2), qf)
-        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None
+        do = _pad_t64(_dense_rows(do)) if T % 64 else _dense_rows(do)
+        dq, dk, dv = ext.attn_bwd(do, q, k, v, o, lse, ctx.causal, T,
+                                  kv_lo=ctx.kv_lo)
+        if T % 64:
+            dq, dk, dv = dq[:, :, :T], dk[:, :, :T], dv[:, :, :T]
+        return dq, dk, dv, None, None
 
 
 def _kernel_supported(q) -> bool:
@@ -191,8 +169,8 @@ def flash_attention(q, k, v, causal: bool = True, window=None,
     elementwise maximum.  Both need ``causal=True`` (ValueError otherwise);
     ``window >= T`` without ``kv_lo`` is the plain causal path."""
     lo = resolve_lo(q.shape[-2], q.device, causal, window, kv_lo)
-    ext = require_ext()
-    if hasattr(ext, "attn_fwd") and _kernel_supported(q):
+    require_ext()
+    if _kernel_supported(q):
         # GQA is native in the kernels: kv may keep fewer heads
         if lo is None:
             return _FlashFn.apply(
@@ -204,8 +182,9 @@ def flash_attention(q, k, v, causal: bool = True, window=None,
     global _warned
     if not _warned:
         log.warning(
-            "attn_fwd not in saturn_amd._C — using explicit-GEMM math "
-            "attention (slower; rebuild with attention.hip)"
+            "attention kernels take bf16 with head size 64, 128 or 256; got "
+            "%s with head size %d — using explicit-GEMM math attention "
+            "(slower)", q.dtype, q.shape[-1]
         )
         _warned = True
     from saturn_amd.ops.functional import attention_math

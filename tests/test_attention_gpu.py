@@ -15,6 +15,7 @@ of them.
 import json
 import math
 import os
+import re
 import subprocess
 import sys
 
@@ -354,6 +355,21 @@ def test_layout_noncontiguous_dout(D, T, form):
         assert _same(a, b)
 
 
+def _off(t, form):
+    """A copy of t whose every row starts 8 B off a 16-B boundary."""
+    if form == "column_slice":
+        wide = torch.zeros(*t.shape[:-1], t.shape[-1] + 8, dtype=t.dtype,
+                           device=DEV)
+        view = wide[..., 4:4 + t.shape[-1]]
+    else:
+        flat = torch.zeros(4 + t.numel(), dtype=t.dtype, device=DEV)
+        view = flat[4:].view(t.shape)
+        assert view.is_contiguous()
+    view.copy_(t)
+    assert view.data_ptr() % 16 == 8 and view.stride(2) % 8 == 0
+    return view
+
+
 @pytest.mark.parametrize("form", ["column_slice", "flat_offset"])
 @pytest.mark.parametrize("D", DS)
 def test_layout_misaligned_rows(D, form):
@@ -368,22 +384,25 @@ def test_layout_misaligned_rows(D, form):
     q, k, v, do = ar.make_inputs("randn", B, H, H, T, D, DEV, seed=13)
     ref = ar.kernel_public(q, k, v, True, do)
 
-    def off(t):
-        if form == "column_slice":
-            wide = torch.zeros(B, H, T, D + 8, dtype=t.dtype, device=DEV)
-            view = wide[..., 4:4 + D]
-        else:
-            flat = torch.zeros(4 + t.numel(), dtype=t.dtype, device=DEV)
-            view = flat[4:].view(t.shape)
-            assert view.is_contiguous()
-        view.copy_(t)
-        assert view.data_ptr() % 16 == 8 and view.stride(2) % 8 == 0
-        return view
-
-    leaves = [off(t).detach().requires_grad_(True) for t in (q, k, v)]
+    leaves = [_off(t, form).detach().requires_grad_(True) for t in (q, k, v)]
     assert all(t.data_ptr() % 16 == 8 for t in leaves)
-    out = ar.flash_fwd_bwd(*leaves, True, off(do))
+    out = ar.flash_fwd_bwd(*leaves, True, _off(do, form))
     for a, b in zip((out, *(t.grad for t in leaves)), ref):
+        assert _same(a, b)
+
+
+@pytest.mark.parametrize("T", [64, 128])            # v1 / v2 forward
+@pytest.mark.parametrize("D", DS)
+def test_layout_misaligned_kv_direct(D, T):
+    """k and v as column slices whose rows start 8 B off a 16-B boundary,
+    straight to ext.attn_fwd / ext.attn_bwd (no wrapper, so nothing is
+    copied).  Only q's pointer is held to 16 B; such k and v are accepted and
+    give the bits of the contiguous call."""
+    q, k, v, do = ar.make_inputs("randn", 1, 2, 2, T, D, DEV, seed=14)
+    ref = ar.ext_fwd_bwd(q, k, v, True, do, T)
+    got = ar.ext_fwd_bwd(q, _off(k, "column_slice"), _off(v, "column_slice"),
+                         True, do, T)
+    for a, b in zip(got, ref):
         assert _same(a, b)
 
 
@@ -469,3 +488,35 @@ def test_switch_in_child_process(setting, key, expect):
     assert not res["failures"], res["failures"]
     assert p.returncode == 0
     assert len(res["cases"]) == 2 * len(ar.SWEEP_CASES)
+
+
+# ---------------------------------------------------------------------------
+# H. attn_bwd checks its arguments on the host, before any launch
+# ---------------------------------------------------------------------------
+BAD_BWD_ARGS = [
+    ("o", "T128", lambda a: a["o"].new_zeros(1, 2, 128, 64)),
+    ("dout", "D128", lambda a: a["dout"].new_zeros(1, 2, 64, 128)),
+    ("lse", "fp64", lambda a: a["lse"].double()),
+    # a [B, T, H] tensor transposed: the right sizes, the wrong strides
+    ("lse", "noncontiguous",
+     lambda a: a["lse"].transpose(1, 2).contiguous().transpose(1, 2)),
+    ("v", "T128", lambda a: a["v"].new_zeros(1, 2, 128, 64)),
+    ("k", "fp32", lambda a: a["k"].float()),
+]
+
+
+@pytest.mark.parametrize("name,what,make", BAD_BWD_ARGS,
+                         ids=[f"{n}-{w}" for n, w, _ in BAD_BWD_ARGS])
+def test_bwd_refuses_bad_argument(name, what, make):
+    q, k, v, do = ar.make_inputs("randn", 1, 2, 2, 64, 64, DEV, seed=15)
+    o, lse = _ext().attn_fwd(q, k, v, True, 64)
+    a = {"dout": do, "q": q, "k": k, "v": v, "o": o, "lse": lse}
+    a[name] = make(a)
+    if name == "lse":
+        assert a["lse"].shape == lse.shape
+    with pytest.raises(RuntimeError) as e:
+        _ext().attn_bwd(a["dout"], a["q"], a["k"], a["v"], a["o"], a["lse"],
+                        True, 64)
+    msg = str(e.value).splitlines()[0]
+    assert msg.startswith("attn_bwd:") and re.search(rf"\b{name}\b", msg), msg
+    torch.cuda.synchronize()                         # and nothing was launched
