@@ -42,15 +42,17 @@ def main() -> None:
         gptj_kw = {"n_layer": 2, "n_embd": 128, "n_head": 4,
                    "vocab_size": 512, "n_ctx": 64, "rotary_dim": 16}
         gpt2_kw = {"preset": "small", "n_layer": 2, "n_ctx": 64}
-        for bs, lr in ((2, 1e-4), (4, 3e-4)):
+        # attn_pdrop: attention dropout, fused into the flash kernels
+        for bs, lr, pdrop in ((2, 1e-4, 0.0), (4, 3e-4, 0.0), (4, 3e-4, 0.1)):
             tasks.append(Task(
-                lambda kwargs=None, kw=gptj_kw: get_gptj_model(kw),
+                lambda kwargs=None, kw=dict(gptj_kw, attn_pdrop=pdrop):
+                    get_gptj_model(kw),
                 make_token_dataloader(batch_size=bs, seq_len=64, vocab=512,
                                       n_batches=8),
                 pretraining_loss,
                 HParams(lr=lr, batch_count=6),
                 gpu_range=[1, 2],
-                name=f"gptj_bs{bs}_lr{lr}",
+                name=f"gptj_bs{bs}_lr{lr}_pdrop{pdrop}",
                 save_dir=save_dir,
             ))
         tasks.append(Task(
@@ -66,15 +68,17 @@ def main() -> None:
         n_gpus, interval = 2, 60
     else:
         # reference WikiText103.py sweeps GPT-J at batch sizes 8..32
-        for bs in (8, 16, 32):
+        # and one attn_pdrop axis at the middle batch size
+        for bs, pdrop in ((8, 0.0), (16, 0.0), (16, 0.1), (32, 0.0)):
             tasks.append(Task(
-                lambda kwargs=None: get_gptj_model({}),
+                lambda kwargs=None, pdrop=pdrop:
+                    get_gptj_model({"attn_pdrop": pdrop}),
                 make_token_dataloader(batch_size=bs, seq_len=512,
                                       vocab=50400, n_batches=64),
                 pretraining_loss,
                 HParams(lr=1e-5, batch_count=200),
                 gpu_range=[1, 2, 4, 8],
-                name=f"gptj6b_bs{bs}",
+                name=f"gptj6b_bs{bs}_pdrop{pdrop}",
                 save_dir=save_dir,
             ))
         tasks.append(Task(

@@ -28,6 +28,7 @@ class GPT2Config:
     n_embd: int = 768
     n_head: int = 12
     n_layer: int = 12
+    attn_pdrop: float = 0.0   # the canonical GPT-2 setting is 0.1
 
 
 PRESETS = {
@@ -45,6 +46,7 @@ class GPT2Attention(nn.Module):
         self.head_dim = cfg.n_embd // cfg.n_head
         self.c_attn = nn.Linear(cfg.n_embd, 3 * cfg.n_embd)
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd)
+        self.attn_pdrop = getattr(cfg, "attn_pdrop", 0.0)
 
     def forward(self, x):
         B, T, E = x.shape
@@ -53,7 +55,10 @@ class GPT2Attention(nn.Module):
         q = q.view(B, T, H, D).transpose(1, 2)
         k = k.view(B, T, H, D).transpose(1, 2)
         v = v.view(B, T, H, D).transpose(1, 2)
-        o = causal_attention(q, k, v)
+        # attn_pdrop = 0 (and eval) makes exactly the call without the keyword
+        drop = ({"dropout_p": self.attn_pdrop}
+                if self.training and self.attn_pdrop > 0 else {})
+        o = causal_attention(q, k, v, **drop)
         return self.c_proj(o.transpose(1, 2).reshape(B, T, E))
 
 
@@ -150,5 +155,9 @@ def get_gpt2_model(kwargs=None):
         from dataclasses import replace
 
         cfg = replace(cfg, n_ctx=kwargs["n_ctx"])
+    if "attn_pdrop" in kwargs:
+        from dataclasses import replace
+
+        cfg = replace(cfg, attn_pdrop=kwargs["attn_pdrop"])
     torch.manual_seed(kwargs.get("seed", 0))
     return GPT2ForCausalLM(cfg)

@@ -51,6 +51,9 @@ class GPTJConfig:
     rotary_dim: int = 64
     embd_pdrop: float = 0.0
     resid_pdrop: float = 0.0
+    # reference attn_pdrop (dropout on the softmax output), fused into the
+    # attention kernels; 0.0 = today's path exactly
+    attn_pdrop: float = 0.0
 
 
 class GPTJAttention(nn.Module):
@@ -65,6 +68,7 @@ class GPTJAttention(nn.Module):
         self.v_proj = nn.Linear(E, E, bias=False)
         self.out_proj = nn.Linear(E, E, bias=False)
         self.n_ctx = cfg.n_ctx
+        self.attn_pdrop = getattr(cfg, "attn_pdrop", 0.0)
         # NOT buffers: model.to(bf16) would quantize the angle tables, and
         # the fused kernel wants the same fp32 [T, half] rows every call
         # (no per-call dtype convert / expand); device placement is lazy.
@@ -90,7 +94,10 @@ class GPTJAttention(nn.Module):
         q = q.transpose(1, 2)  # [B, H, T, D]
         k = k.transpose(1, 2)
         v = v.transpose(1, 2)
-        o = causal_attention(q, k, v)
+        # attn_pdrop = 0 (and eval) makes exactly the call without the keyword
+        drop = ({"dropout_p": self.attn_pdrop}
+                if self.training and self.attn_pdrop > 0 else {})
+        o = causal_attention(q, k, v, **drop)
         o = o.transpose(1, 2).reshape(B, T, -1)  # -1: heads may be TP-sharded
         return self.out_proj(o)
 
@@ -163,6 +170,9 @@ class GPTJBlock(nn.Module):
         if not (h.is_cuda and h.dtype == torch.bfloat16 and h.dim() == 3):
             return False
         if self.drop.p != 0.0:
+            return False
+        # the block node calls attn_fwd directly and stays dropout-free
+        if self.training and attn.attn_pdrop > 0:
             return False
         from saturn_amd.parallel.sequence import sp_world
 
@@ -277,6 +287,7 @@ def get_gptj_model(kwargs=None):
         rotary_dim=kwargs.get("rotary_dim", 64),
         embd_pdrop=kwargs.get("embd_pdrop", 0.0),
         resid_pdrop=kwargs.get("resid_pdrop", 0.0),
+        attn_pdrop=kwargs.get("attn_pdrop", 0.0),
     )
     torch.manual_seed(kwargs.get("seed", 0))
     return GPTJForCausalLM(cfg)

@@ -36,6 +36,8 @@ class LlamaConfig:
     rope_theta: float = 500000.0
     # Mistral-style sliding window: row t attends keys t-window+1 .. t
     sliding_window: Optional[int] = None
+    # attention dropout (not supported together with sliding_window)
+    attn_pdrop: float = 0.0
 
 
 PRESETS = {
@@ -62,6 +64,7 @@ class LlamaAttention(nn.Module):
         self.n_kv = cfg.n_kv_head
         self.head_dim = cfg.n_embd // cfg.n_head
         self.sliding_window = getattr(cfg, "sliding_window", None)
+        self.attn_pdrop = getattr(cfg, "attn_pdrop", 0.0)
         E = cfg.n_embd
         self.q_proj = nn.Linear(E, self.n_head * self.head_dim, bias=False)
         self.k_proj = nn.Linear(E, self.n_kv * self.head_dim, bias=False)
@@ -86,9 +89,12 @@ class LlamaAttention(nn.Module):
         cos, sin = self._rope(x.device)
         q = apply_rope(q, cos, sin, half_style=True)
         k = apply_rope(k, cos, sin, half_style=True)
+        # attn_pdrop = 0 (and eval) makes exactly the call without the keyword
+        drop = ({"dropout_p": self.attn_pdrop}
+                if self.training and self.attn_pdrop > 0 else {})
         o = causal_attention(
             q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
-            window=self.sliding_window,
+            window=self.sliding_window, **drop,
         )
         return self.o_proj(o.transpose(1, 2).reshape(B, T, -1))
 
@@ -177,7 +183,8 @@ def get_llama_model(kwargs=None):
     from dataclasses import replace
 
     cfg = PRESETS[kwargs.get("preset", "8b")]
-    for key in ("n_layer", "n_ctx", "vocab_size", "sliding_window"):
+    for key in ("n_layer", "n_ctx", "vocab_size", "sliding_window",
+                "attn_pdrop"):
         if key in kwargs:
             cfg = replace(cfg, **{key: kwargs[key]})
     torch.manual_seed(kwargs.get("seed", 0))

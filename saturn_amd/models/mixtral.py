@@ -40,6 +40,8 @@ class MixtralConfig:
     top_k: int = 2
     # Mistral-style sliding window: row t attends keys t-window+1 .. t
     sliding_window: Optional[int] = None
+    # attention dropout (not supported together with sliding_window)
+    attn_pdrop: float = 0.0
 
 
 PRESETS = {
@@ -204,6 +206,10 @@ def get_mixtral_model(kwargs=None):
             from dataclasses import replace
 
             cfg = replace(cfg, sliding_window=kwargs["sliding_window"])
+        if "attn_pdrop" in kwargs:
+            from dataclasses import replace
+
+            cfg = replace(cfg, attn_pdrop=kwargs["attn_pdrop"])
     else:
         cfg = MixtralConfig(
             vocab_size=kwargs.get("vocab_size", 32000),
@@ -216,6 +222,7 @@ def get_mixtral_model(kwargs=None):
             n_expert=kwargs.get("n_expert", 8),
             top_k=kwargs.get("top_k", 2),
             sliding_window=kwargs.get("sliding_window"),
+            attn_pdrop=kwargs.get("attn_pdrop", 0.0),
         )
     torch.manual_seed(kwargs.get("seed", 0))
     return MixtralForCausalLM(cfg)

@@ -26,6 +26,7 @@ class ViTConfig:
     n_head: int = 16
     n_layer: int = 24
     n_classes: int = 1000
+    attn_pdrop: float = 0.0
 
 
 class ViTBlock(nn.Module):
@@ -42,6 +43,7 @@ class ViTBlock(nn.Module):
         )
         self.n_head = cfg.n_head
         self.head_dim = cfg.n_embd // cfg.n_head
+        self.attn_pdrop = getattr(cfg, "attn_pdrop", 0.0)
 
     def forward(self, x):
         B, T, E = x.shape
@@ -50,7 +52,11 @@ class ViTBlock(nn.Module):
         q = q.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         k = k.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         v = v.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
-        o = full_attention(q, k, v).transpose(1, 2).reshape(B, T, E)
+        # attn_pdrop = 0 (and eval) makes exactly the call without the keyword
+        drop = ({"dropout_p": self.attn_pdrop}
+                if self.training and self.attn_pdrop > 0 else {})
+        o = full_attention(q, k, v, **drop)
+        o = o.transpose(1, 2).reshape(B, T, E)
         x = x + self.proj(o)
         x = x + self.mlp(self.ln_2(x))
         return x
@@ -95,6 +101,7 @@ def get_vit_model(kwargs=None):
         n_embd=kwargs.get("n_embd", 1024),
         n_head=kwargs.get("n_head", 16),
         img_size=kwargs.get("img_size", 224),
+        attn_pdrop=kwargs.get("attn_pdrop", 0.0),
     )
     torch.manual_seed(kwargs.get("seed", 0))
     return ViTForImageClassification(cfg)

@@ -36,6 +36,7 @@
 
 #include <atomic>
 
+#include "attn_rng.h"
 #include "common.h"
 #include "ops.h"
 
@@ -138,7 +139,7 @@ struct AttnLds {
   unsigned short p[4][WROWS][KBLK];
 };
 
-template <int D, bool LO>
+template <int D, bool LO, bool DROP>
 __launch_bounds__(256, 2)
 __global__ void attn_fwd_kernel(const unsigned short* __restrict__ Q,
                                 const unsigned short* __restrict__ K,
@@ -148,7 +149,8 @@ __global__ void attn_fwd_kernel(const unsigned short* __restrict__ Q,
                                 int n_kv, float scale, int causal,
                                 int kv_len, TStr qs, TStr ks, TStr vs,
                                 TStr os, const int* __restrict__ KVLO,
-                                long lo_sb) {
+                                long lo_sb, unsigned long long seed,
+                                unsigned thr, float drop_r) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   AttnLds<D>& lds = *reinterpret_cast<AttnLds<D>*>(smem);
 
@@ -282,8 +284,21 @@ __global__ void attn_fwd_kernel(const unsigned short* __restrict__ Q,
         ps += __shfl_xor(ps, off, 64);
       l_reg[reg] = l_reg[reg] * al + ps;
       m_reg[reg] = m_new;
-      lds.p[wid][row][r] = f2us(p0);
-      lds.p[wid][row][16 + r] = f2us(p1);
+      if constexpr (DROP) {
+        // attention dropout: m, l and LSE above come from the undropped
+        // scores; a dropped P is 0 in the PV MFMA and 1/(1-p) waits for the
+        // epilogue.  This lane's two keys lie in different draws.
+        const unsigned long long rk = attn_rng_row(seed, bh, qrow);
+        const bool z0 =
+            attn_rng_keep(attn_rng_draw(rk, kv0 + r), kv0 + r, thr);
+        const bool z1 =
+            attn_rng_keep(attn_rng_draw(rk, kv0 + 16 + r), kv0 + 16 + r, thr);
+        lds.p[wid][row][r] = z0 ? f2us(p0) : (unsigned short)0;
+        lds.p[wid][row][16 + r] = z1 ? f2us(p1) : (unsigned short)0;
+      } else {
+        lds.p[wid][row][r] = f2us(p0);
+        lds.p[wid][row][16 + r] = f2us(p1);
+      }
 #pragma unroll
       for (int dt = 0; dt < D / 16; ++dt) otile[dt][reg] *= al;
     }
@@ -303,6 +318,7 @@ __global__ void attn_fwd_kernel(const unsigned short* __restrict__ Q,
   for (int reg = 0; reg < 4; ++reg) {
     int row = qg * 4 + reg;
     float linv = 1.f / l_reg[reg];
+    if constexpr (DROP) linv = drop_r / l_reg[reg];
 #pragma unroll
     for (int dt = 0; dt < D / 16; ++dt)
       Oh[(long)(q0 + row) * os.st + dt * 16 + r] =
@@ -338,7 +354,7 @@ struct AttnV2Lds {
   unsigned short v[KBLK][D + 8];
 };
 
-template <int D, bool LO>
+template <int D, bool LO, bool DROP>
 __launch_bounds__(256, 2)
 __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
                                    const unsigned short* __restrict__ K,
@@ -349,7 +365,8 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
                                    int causal, int kv_len, TStr qs,
                                    TStr ks, TStr vs,
                                    TStr os, const int* __restrict__ KVLO,
-                                   long lo_sb) {
+                                   long lo_sb, unsigned long long seed,
+                                   unsigned thr, float drop_r) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   AttnV2Lds<D>& lds = *reinterpret_cast<AttnV2Lds<D>*>(smem);
 
@@ -499,6 +516,22 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
       const unsigned hi2 = f2us(p[2 * i + 1]);
       pk[i] = lo | (hi2 << 16);
     }
+    if constexpr (DROP) {
+      // attention dropout on the rounded P (m, l, LSE stay undropped).
+      // regs 4g..4g+3 are the aligned keys kv0 + 8g + 4hi + 0..3 of this
+      // lane's row: one draw per four scores, its 16-bit fields in key order.
+      const unsigned long long rk = attn_rng_row(seed, bh, q_glob);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int key0 = kv0 + 8 * g + 4 * hi;
+        const unsigned long long dr = attn_rng_draw(rk, key0);
+#pragma unroll
+        for (int w = 0; w < 2; ++w)   // pk[2g + w] = keys key0 + 2w, + 2w + 1
+          pk[2 * g + w] &=
+              (attn_rng_keep4(dr, 2 * w, thr) ? 0x0000ffffu : 0u) |
+              (attn_rng_keep4(dr, 2 * w + 1, thr) ? 0xffff0000u : 0u);
+      }
+    }
     // tile g (g=0: keys 0-15, g=1: keys 16-31): lane pairs pk[4g+0..3] hold
     //   hi=0: (0,1),(2,3),(8,9),(10,11)   [+16 for g=1]
     //   hi=1: (4,5),(6,7),(12,13),(14,15)
@@ -567,7 +600,7 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
 
   // ---- epilogue
   unsigned short* Oh = O + b * os.sb + h * os.sh;
-  const float linv_own = 1.f / l_row;
+  const float linv_own = DROP ? drop_r / l_row : 1.f / l_row;
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
     const int row = (reg & 3) + 8 * (reg >> 2) + 4 * hi;
@@ -669,7 +702,7 @@ __global__ void attn_delta_kernel(const unsigned short* __restrict__ dO,
   }
 }
 
-template <int D, bool TR16, bool VL2, bool LO>
+template <int D, bool TR16, bool VL2, bool LO, bool DROP>
 __launch_bounds__(256, 2)
 __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
                                 const unsigned short* __restrict__ Q,
@@ -685,7 +718,9 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
                                 int kv_len, TStr dos,
                                 TStr qs, TStr ks, TStr vs,
                                 TStr dks, TStr dvs,
-                                const int* __restrict__ KVLO, long lo_sb) {
+                                const int* __restrict__ KVLO, long lo_sb,
+                                unsigned long long seed, unsigned thr,
+                                float drop_r) {
   using namespace bwd;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool HASV = (D <= 128) && !VL2;  // V tile LDS-resident?
@@ -788,6 +823,12 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
         st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak, bq, st, 0, 0, 0);
         dpt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bdo, dpt, 0, 0, 0);
       }
+      // attention dropout: this lane's four keys (reg) are one aligned group
+      // of q row q0 + n*16 + r, so one draw regenerates the forward's Z
+      unsigned long long zdraw = 0;
+      if constexpr (DROP)
+        zdraw = attn_rng_draw(attn_rng_row(seed, bh, q0 + n * 16 + r),
+                              kv0 + wid * 16 + qg * 4);
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
         const int key_loc = qg * 4 + reg;           // within wave's 16 keys
@@ -799,9 +840,19 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
         if (seen) {
           p = __expf(scale * st[reg] - lds.lse_t[n * 16 + r]);
         }
-        const float dsv = p * (dpt[reg] - lds.delta_t[n * 16 + r]) * scale;
-        lds.pt[wid][key_loc][n * 16 + r] = f2us(p);
-        lds.dst[wid * 16 + key_loc][n * 16 + r] = f2us(dsv);
+        if constexpr (DROP) {
+          // dV takes P o Z (its 1/(1-p) waits for the epilogue);
+          // dS = P o (r Z o dP - delta) * scale
+          const bool z = attn_rng_keep4(zdraw, reg, thr);
+          const float dpz = z ? drop_r * dpt[reg] : 0.f;
+          const float dsv = p * (dpz - lds.delta_t[n * 16 + r]) * scale;
+          lds.pt[wid][key_loc][n * 16 + r] = z ? f2us(p) : (unsigned short)0;
+          lds.dst[wid * 16 + key_loc][n * 16 + r] = f2us(dsv);
+        } else {
+          const float dsv = p * (dpt[reg] - lds.delta_t[n * 16 + r]) * scale;
+          lds.pt[wid][key_loc][n * 16 + r] = f2us(p);
+          lds.dst[wid * 16 + key_loc][n * 16 + r] = f2us(dsv);
+        }
       }
     }
 
@@ -842,6 +893,10 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
   // ---- epilogue: write dK, dV.  With GQA (several q heads per kv head)
   // the partials accumulate into fp32 buffers with atomics; otherwise a
   // direct bf16 store.
+  if constexpr (DROP) {
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt) acc_dv[dt] *= drop_r;
+  }
   if (n_kv != n_heads) {
     float* dKh = dKf + b * dks.sb + h_kv * dks.sh;
     float* dVh = dVf + b * dvs.sb + h_kv * dvs.sh;
@@ -906,7 +961,7 @@ struct AttnDqLds {
   float delta_t[dq::QB];
 };
 
-template <int D, bool TR16, bool GKV, bool LO>
+template <int D, bool TR16, bool GKV, bool LO, bool DROP>
 __launch_bounds__(256, GKV ? 3 : (D <= 128 ? 2 : 1))
 __global__ void attn_dq_kernel(const unsigned short* __restrict__ dO,
                                const unsigned short* __restrict__ Q,
@@ -918,7 +973,9 @@ __global__ void attn_dq_kernel(const unsigned short* __restrict__ dO,
                                int n_heads, int n_kv, float scale, int causal,
                                int kv_len, TStr dos, TStr qs, TStr ks,
                                TStr vs, TStr dqs,
-                               const int* __restrict__ KVLO, long lo_sb) {
+                               const int* __restrict__ KVLO, long lo_sb,
+                               unsigned long long seed, unsigned thr,
+                               float drop_r) {
   using namespace dq;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   AttnDqLds<D, GKV>& lds = *reinterpret_cast<AttnDqLds<D, GKV>*>(smem);
@@ -1028,6 +1085,12 @@ __global__ void attn_dq_kernel(const unsigned short* __restrict__ dO,
       const int q_glob = q0 + wid * 16 + r;
       const float l_q = lds.lse_t[wid * 16 + r];
       const float d_q = lds.delta_t[wid * 16 + r];
+      // attention dropout: the same dS as the dK/dV kernel, Z recomputed
+      // here; the four keys on reg are one aligned group of this lane's row
+      unsigned long long zdraw = 0;
+      if constexpr (DROP)
+        zdraw = attn_rng_draw(attn_rng_row(seed, bh, q_glob),
+                              k0 + n * 16 + qg * 4);
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
         const int key_glob = k0 + n * 16 + qg * 4 + reg;
@@ -1035,7 +1098,13 @@ __global__ void attn_dq_kernel(const unsigned short* __restrict__ dO,
         bool seen = (!causal || q_glob >= key_glob) && key_glob < kv_len;
         if constexpr (LO) seen = seen && key_glob >= lo_q;
         if (seen) p = __expf(scale * st[reg] - l_q);
-        ds_sub[n][reg] = p * (dpt[reg] - d_q) * scale;
+        if constexpr (DROP) {
+          const float dpz =
+              attn_rng_keep4(zdraw, reg, thr) ? drop_r * dpt[reg] : 0.f;
+          ds_sub[n][reg] = p * (dpz - d_q) * scale;
+        } else {
+          ds_sub[n][reg] = p * (dpt[reg] - d_q) * scale;
+        }
       }
     }
 
@@ -1141,11 +1210,25 @@ struct AttnPlan {
   bool vl2;     // dK/dV: V from L2
   bool gkv;     // dQ: K/V/Q/dO fragments from L2
   bool lo;      // the kv_lo instantiations
+  bool drop;    // the attention-dropout instantiations
 };
 // bwd: the plan will select backward kernels (attn_bwd, attn_dispatch).  The
 // kv_lo backward is built for the default switches only and refused by name
-// otherwise; the kv_lo forward is built for every setting.
-static AttnPlan attn_plan(int T, int D, bool has_lo, bool bwd = true) {
+// otherwise; the kv_lo forward is built for every setting.  Attention
+// dropout follows the same rule (SAMD_ATTN_V2=0 simply takes the v1 forward)
+// and is not built together with kv_lo.
+static AttnPlan attn_plan(int T, int D, bool has_lo, bool bwd = true,
+                          bool has_drop = false) {
+  TORCH_CHECK(!(has_lo && has_drop), bwd ? "attn_bwd" : "attn_fwd",
+              ": dropout_p > 0 is not built together with kv_lo");
+  if (has_drop && bwd) {
+    TORCH_CHECK(sw_tr16(), "attn_bwd: attention dropout is not built for "
+                "SAMD_ATTN_BWD_TR16=0; unset the switch");
+    TORCH_CHECK(!sw_vl2(), "attn_bwd: attention dropout is not built for "
+                "SAMD_ATTN_BWD_VL2=1; unset the switch");
+    TORCH_CHECK(!sw_dq_gkv(), "attn_bwd: attention dropout is not built for "
+                "SAMD_ATTN_DQ_GKV=1; unset the switch");
+  }
   if (has_lo && bwd) {
     TORCH_CHECK(sw_tr16(), "attn_bwd: kv_lo is not built for "
                 "SAMD_ATTN_BWD_TR16=0; unset the switch");
@@ -1155,7 +1238,8 @@ static AttnPlan attn_plan(int T, int D, bool has_lo, bool bwd = true) {
                 "SAMD_ATTN_DQ_GKV=1; unset the switch");
   }
   return AttnPlan{sw_v2() && T % 128 == 0 && D <= 128, sw_tr16() && D <= 128,
-                  sw_vl2() && D <= 128, sw_dq_gkv() && D > 128, has_lo};
+                  sw_vl2() && D <= 128, sw_dq_gkv() && D > 128, has_lo,
+                  has_drop};
 }
 
 // One launched instantiation.  Everything here comes from the template
@@ -1169,43 +1253,47 @@ struct Variant {
   // MaxDynamicSharedMemorySize set for this instantiation?  nullptr: never
   // needed (forward and delta, < 64 KB)
   std::atomic<bool>* lds_raised;
-  const char* stem;  // reported as stem<args...>, then ",1" for LO
+  // reported as stem<args...>, then ",1" for LO or ",0,1" for DROP
+  const char* stem;
   int nargs, args[3];
-  bool lo;
+  bool lo, drop;
 };
-using FwdVariant = Variant<decltype(attn_fwd_kernel<64, false>)>;
+using FwdVariant = Variant<decltype(attn_fwd_kernel<64, false, false>)>;
 using DeltaVariant = Variant<decltype(attn_delta_kernel<64>)>;
-using BwdVariant = Variant<decltype(attn_bwd_kernel<64, false, false, false>)>;
-using DqVariant = Variant<decltype(attn_dq_kernel<64, false, false, false>)>;
+using BwdVariant =
+    Variant<decltype(attn_bwd_kernel<64, false, false, false, false>)>;
+using DqVariant =
+    Variant<decltype(attn_dq_kernel<64, false, false, false, false>)>;
 
-template <int D, bool LO>
+template <int D, bool LO, bool DROP = false>
 static FwdVariant fwd_v1_of() {
-  return {&attn_fwd_kernel<D, LO>, (int)sizeof(AttnLds<D>), QBLK, nullptr,
-          "attn_fwd_kernel", 1, {D}, LO};
+  return {&attn_fwd_kernel<D, LO, DROP>, (int)sizeof(AttnLds<D>), QBLK,
+          nullptr, "attn_fwd_kernel", 1, {D}, LO, DROP};
 }
-template <int D, bool LO>
+template <int D, bool LO, bool DROP = false>
 static FwdVariant fwd_v2_of() {
-  return {&attn_fwd_v2_kernel<D, LO>, (int)sizeof(AttnV2Lds<D>), 4 * 32,
-          nullptr, "attn_fwd_v2_kernel", 1, {D}, LO};
+  return {&attn_fwd_v2_kernel<D, LO, DROP>, (int)sizeof(AttnV2Lds<D>), 4 * 32,
+          nullptr, "attn_fwd_v2_kernel", 1, {D}, LO, DROP};
 }
 template <int D>
 static DeltaVariant delta_of() {
   return {&attn_delta_kernel<D>, 0, 4, nullptr, "attn_delta_kernel", 1, {D},
-          false};
+          false, false};
 }
-template <int D, bool TR16, bool VL2, bool LO>
+template <int D, bool TR16, bool VL2, bool LO, bool DROP = false>
 static BwdVariant bwd_of() {
   static std::atomic<bool> raised{false};
   constexpr bool HASV = (D <= 128) && !VL2;  // as in the kernel
-  return {&attn_bwd_kernel<D, TR16, VL2, LO>,
+  return {&attn_bwd_kernel<D, TR16, VL2, LO, DROP>,
           (int)sizeof(AttnBwdLdsT<D, HASV, LO>), bwd::KB, &raised,
-          "attn_bwd_kernel", 3, {D, TR16, VL2}, LO};
+          "attn_bwd_kernel", 3, {D, TR16, VL2}, LO, DROP};
 }
-template <int D, bool TR16, bool GKV, bool LO>
+template <int D, bool TR16, bool GKV, bool LO, bool DROP = false>
 static DqVariant dq_of() {
   static std::atomic<bool> raised{false};
-  return {&attn_dq_kernel<D, TR16, GKV, LO>, (int)sizeof(AttnDqLds<D, GKV>),
-          dq::QB, &raised, "attn_dq_kernel", 3, {D, TR16, GKV}, LO};
+  return {&attn_dq_kernel<D, TR16, GKV, LO, DROP>,
+          (int)sizeof(AttnDqLds<D, GKV>), dq::QB, &raised, "attn_dq_kernel", 3,
+          {D, TR16, GKV}, LO, DROP};
 }
 
 // f(D as a compile-time constant); D is one of 64, 128, 256 by now.
@@ -1222,8 +1310,10 @@ static FwdVariant fwd_variant(const AttnPlan& p, int D) {
   return with_d(D, [&](auto d) -> FwdVariant {
     constexpr int DD = decltype(d)::value;
     if constexpr (DD <= 128) {
+      if (p.fwd_v2 && p.drop) return fwd_v2_of<DD, false, true>();
       if (p.fwd_v2) return p.lo ? fwd_v2_of<DD, true>() : fwd_v2_of<DD, false>();
     }
+    if (p.drop) return fwd_v1_of<DD, false, true>();
     return p.lo ? fwd_v1_of<DD, true>() : fwd_v1_of<DD, false>();
   });
 }
@@ -1234,6 +1324,7 @@ static BwdVariant bwd_variant(const AttnPlan& p, int D) {
   return with_d(D, [&](auto d) -> BwdVariant {
     constexpr int DD = decltype(d)::value;
     if (p.lo) return bwd_of<DD, (DD <= 128), false, true>();
+    if (p.drop) return bwd_of<DD, (DD <= 128), false, false, true>();
     if constexpr (DD <= 128) {
       if (p.tr16)
         return p.vl2 ? bwd_of<DD, true, true, false>()
@@ -1247,6 +1338,7 @@ static DqVariant dq_variant(const AttnPlan& p, int D) {
   return with_d(D, [&](auto d) -> DqVariant {
     constexpr int DD = decltype(d)::value;
     if (p.lo) return dq_of<DD, (DD <= 128), false, true>();
+    if (p.drop) return dq_of<DD, (DD <= 128), false, false, true>();
     if constexpr (DD <= 128) {
       if (p.tr16) return dq_of<DD, true, false, false>();
     } else {
@@ -1260,18 +1352,19 @@ template <class Fn>
 static std::string name_of(const Variant<Fn>& v) {
   std::string s = std::string(v.stem) + "<" + std::to_string(v.args[0]);
   for (int i = 1; i < v.nargs; ++i) s += "," + std::to_string(v.args[i]);
-  return s + (v.lo ? ",1>" : ">");
+  return s + (v.drop ? ",0,1>" : v.lo ? ",1>" : ">");
 }
 
 // The kernel instantiations attn_fwd / attn_bwd launch for a padded T and
 // a head size D in this process, space-separated.
 // has_lo: the instantiations taken when a kv_lo bound is given (the names
-// then carry the LO template argument).
-std::string attn_dispatch(int64_t T, int64_t D, bool has_lo) {
+// then carry the LO template argument).  has_drop: those taken with
+// dropout_p > 0 (the names carry LO = 0 and the DROP argument).
+std::string attn_dispatch(int64_t T, int64_t D, bool has_lo, bool has_drop) {
   TORCH_CHECK(T > 0 && T % QBLK == 0, "attn_dispatch: T must be a multiple of 64");
   TORCH_CHECK(D == 64 || D == 128 || D == 256, "attn_dispatch: D in {64,128,256}");
   const int d = (int)D;
-  const AttnPlan p = attn_plan((int)T, d, has_lo);
+  const AttnPlan p = attn_plan((int)T, d, has_lo, /*bwd=*/true, has_drop);
   return name_of(fwd_variant(p, d)) + " " + name_of(delta_variant(d)) + " " +
          name_of(bwd_variant(p, d)) + " " + name_of(dq_variant(p, d));
 }
@@ -1324,6 +1417,30 @@ static LoArg lo_arg(const c10::optional<at::Tensor>& kv_lo,
   return LoArg{lo.data_ptr<int>(), lo.dim() == 2 ? (long)T : 0L};
 }
 
+// Attention dropout (attn_rng.h): a 16-bit threshold, so the effective rate
+// is thr / 65536, and r = 1 / (1 - thr/65536) computed in double.  thr == 0
+// (p below 2^-17) is no dropout: the plain instantiations are launched.
+struct DropArg {
+  unsigned long long seed;
+  unsigned thr;
+  float r;
+};
+static DropArg drop_arg(double p, int64_t seed, const at::Tensor& q,
+                        const char* who) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, who, ": dropout_p must be in [0, 1), got ",
+              p);
+  const unsigned thr =
+      std::min(65535u, (unsigned)std::floor(p * 65536.0 + 0.5));
+  if (thr == 0) return DropArg{0ull, 0u, 1.f};
+  // the counter packs (bh, i, j >> 2) into 24 + 20 + 18 bits
+  TORCH_CHECK(q.size(2) <= (int64_t(1) << ATTN_RNG_MAX_T_LOG2), who,
+              ": attention dropout needs T <= 2^20");
+  TORCH_CHECK(q.size(0) * q.size(1) < (int64_t(1) << ATTN_RNG_MAX_BH_LOG2),
+              who, ": attention dropout needs B * H < 2^24");
+  return DropArg{(unsigned long long)seed, thr,
+                 (float)(65536.0 / (65536.0 - (double)thr))};
+}
+
 // The q/k/v checks of both entry points (who: "attn_fwd" / "attn_bwd").
 // kv_len < T marks ragged sequences: q/k/v are zero-padded to a 64 multiple
 // by the wrapper and keys >= kv_len are masked out in-kernel; kv_len <= 0
@@ -1367,9 +1484,11 @@ static AttnDims check_qkv(const at::Tensor& q, const at::Tensor& k,
 
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  bool causal, int64_t kv_len,
-                                 c10::optional<at::Tensor> kv_lo) {
+                                 c10::optional<at::Tensor> kv_lo,
+                                 double dropout_p, int64_t seed) {
   const auto [B, H, Hkv, T, D] = check_qkv(q, k, v, kv_len, "attn_fwd");
   const LoArg lo = lo_arg(kv_lo, q, causal, "attn_fwd");
+  const DropArg dr = drop_arg(dropout_p, seed, q, "attn_fwd");
 
   // output physically [B, T, H, D]: the model's post-attention
   // transpose(1,2).reshape is then a zero-copy view
@@ -1378,19 +1497,21 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   auto lse = at::empty({B, H, T}, q.options().dtype(at::kFloat));
   const float scale = 1.f / sqrtf((float)D);
 
-  const FwdVariant fv =
-      fwd_variant(attn_plan(T, D, lo.ptr != nullptr, /*bwd=*/false), D);
+  const FwdVariant fv = fwd_variant(
+      attn_plan(T, D, lo.ptr != nullptr, /*bwd=*/false, dr.thr != 0), D);
   launch(fv, dim3(B * H, T / fv.rows), at::hip::getCurrentHIPStream().stream(),
          bf16_in(q), bf16_in(k), bf16_in(v), bf16_out(o),
          lse.data_ptr<float>(), T, H, Hkv, scale, causal ? 1 : 0, (int)kv_len,
-         str_of(q), str_of(k), str_of(v), str_of(o), lo.ptr, lo.sb);
+         str_of(q), str_of(k), str_of(v), str_of(o), lo.ptr, lo.sb, dr.seed,
+         dr.thr, dr.r);
   return {o, lse};
 }
 
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  at::Tensor v, at::Tensor o, at::Tensor lse,
                                  bool causal, int64_t kv_len,
-                                 c10::optional<at::Tensor> kv_lo) {
+                                 c10::optional<at::Tensor> kv_lo,
+                                 double dropout_p, int64_t seed) {
   const auto [B, H, Hkv, T, D] = check_qkv(q, k, v, kv_len, "attn_bwd");
   TORCH_CHECK(dout.sizes() == q.sizes(), "attn_bwd: dout must have q's sizes");
   TORCH_CHECK(o.sizes() == q.sizes(), "attn_bwd: o must have q's sizes");
@@ -1406,7 +1527,9 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                   lse.size(2) == T && lse.is_contiguous(),
               "attn_bwd: lse must be a contiguous [B, H, T] tensor");
   const LoArg lo = lo_arg(kv_lo, q, causal, "attn_bwd");
-  const AttnPlan plan = attn_plan(T, D, lo.ptr != nullptr);
+  const DropArg dr = drop_arg(dropout_p, seed, q, "attn_bwd");
+  const AttnPlan plan =
+      attn_plan(T, D, lo.ptr != nullptr, /*bwd=*/true, dr.thr != 0);
 
   auto delta = at::empty({B, H, T}, q.options().dtype(at::kFloat));
   // grads physically [B, T, H, D] (matches the projection layout upstream,
@@ -1435,7 +1558,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
          bf16_in(k), bf16_in(v), lse.data_ptr<float>(),
          delta.data_ptr<float>(), bf16_out(dq), T, H, Hkv, scale, c, kvl,
          str_of(dout), str_of(q), str_of(k), str_of(v), str_of(dq), lo.ptr,
-         lo.sb);
+         lo.sb, dr.seed, dr.thr, dr.r);
   const BwdVariant bv = bwd_variant(plan, D);
   launch(bv, dim3(B * H, T / bv.rows), stream, bf16_in(dout), bf16_in(q),
          bf16_in(k), bf16_in(v), lse.data_ptr<float>(),
@@ -1444,7 +1567,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
          gqa ? dv_f32.data_ptr<float>() : nullptr, T, H, Hkv, scale, c, kvl,
          str_of(dout), str_of(q), str_of(k), str_of(v),
          gqa ? str_of(dk_f32) : str_of(dk), gqa ? str_of(dv_f32) : str_of(dv),
-         lo.ptr, lo.sb);
+         lo.ptr, lo.sb, dr.seed, dr.thr, dr.r);
   if (gqa) return {dq, dk_f32.to(at::kBFloat16), dv_f32.to(at::kBFloat16)};
   return {dq, dk, dv};
 }

@@ -35,14 +35,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gelu_bwd", &samd::gelu_bwd, "fused tanh-approx GELU backward");
   m.def("attn_fwd", &samd::attn_fwd, "fused flash attention forward",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
-        py::arg("kv_len") = -1, py::arg("kv_lo") = py::none());
+        py::arg("kv_len") = -1, py::arg("kv_lo") = py::none(),
+        py::arg("dropout_p") = 0.0, py::arg("seed") = 0);
   m.def("attn_dispatch", &samd::attn_dispatch,
         "kernel instantiations attn_fwd/attn_bwd launch for (padded T, D)",
-        py::arg("T"), py::arg("D"), py::arg("has_lo") = false);
+        py::arg("T"), py::arg("D"), py::arg("has_lo") = false,
+        py::arg("has_drop") = false);
   m.def("attn_bwd", &samd::attn_bwd, "fused flash attention backward",
         py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o"), py::arg("lse"), py::arg("causal"),
-        py::arg("kv_len") = -1, py::arg("kv_lo") = py::none());
+        py::arg("kv_len") = -1, py::arg("kv_lo") = py::none(),
+        py::arg("dropout_p") = 0.0, py::arg("seed") = 0);
   m.def("add3", &samd::add3, "fused 3-way residual add");
   m.def("swiglu_fwd", &samd::swiglu_fwd, "fused silu(gate)*up");
   m.def("swiglu_bwd", &samd::swiglu_bwd, "fused SwiGLU backward");

@@ -9,19 +9,13 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "attn_rng.h"  // mix64, shared with the attention dropout
 #include "common.h"
 #include "ops.h"
 
 namespace samd {
 
 typedef __attribute__((ext_vector_type(8))) short d8v;
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
 
 // two elements per 64-bit draw: lane handles 8 elements = 4 draws
 template <typename T, bool BWD>

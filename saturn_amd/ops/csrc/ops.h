@@ -54,12 +54,15 @@ at::Tensor gelu_bwd(at::Tensor dy, at::Tensor x);
 // attention.hip
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  bool causal, int64_t kv_len,
-                                 c10::optional<at::Tensor> kv_lo);
+                                 c10::optional<at::Tensor> kv_lo,
+                                 double dropout_p = 0.0, int64_t seed = 0);
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  at::Tensor v, at::Tensor o, at::Tensor lse,
                                  bool causal, int64_t kv_len,
-                                 c10::optional<at::Tensor> kv_lo);
-std::string attn_dispatch(int64_t T, int64_t D, bool has_lo);
+                                 c10::optional<at::Tensor> kv_lo,
+                                 double dropout_p = 0.0, int64_t seed = 0);
+std::string attn_dispatch(int64_t T, int64_t D, bool has_lo = false,
+                          bool has_drop = false);
 
 // add3.hip, swiglu.hip, embedding.hip, dropout.hip
 at::Tensor add3(at::Tensor a, at::Tensor b, at::Tensor c);

@@ -243,13 +243,22 @@ def apply_rope(
 # fallback below (explicit GEMMs + softmax, fp32 accum like the reference's
 # GPTJ.py:164-191) is used on CPU and as the numerics reference.
 # ---------------------------------------------------------------------------
-def attention_math(q, k, v, causal: bool = True, kv_lo=None) -> torch.Tensor:
+def attention_math(q, k, v, causal: bool = True, kv_lo=None,
+                   dropout_p: float = 0.0, seed=None) -> torch.Tensor:
     """q,k,v: [B, H, T, D].  fp32 score math, returns q.dtype.
 
     ``kv_lo`` (integer [T] or [B, T], needs ``causal``): row t sees keys
-    kv_lo[b,t] .. t instead of 0 .. t."""
+    kv_lo[b,t] .. t instead of 0 .. t.
+
+    ``dropout_p`` / ``seed``: attention dropout on the fp32 probabilities
+    with the kernels' own mask (``flash.dropout_keep``) and factor, so the
+    CPU path and the fused path drop the same entries for the same seed."""
     if kv_lo is not None and not causal:
         raise ValueError("kv_lo needs causal=True")
+    if dropout_p:
+        from saturn_amd.ops import flash
+
+        dropout_p = flash.check_dropout(dropout_p, None, kv_lo)
     scale = 1.0 / (q.shape[-1] ** 0.5)
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
     if causal:
@@ -261,24 +270,35 @@ def attention_math(q, k, v, causal: bool = True, kv_lo=None) -> torch.Tensor:
             mask = mask & lo_mask(kv_lo)
         s = s.masked_fill(~mask, float("-inf"))
     p = torch.softmax(s, dim=-1)
+    if dropout_p:
+        B, H, T = q.shape[0], q.shape[1], q.shape[-2]
+        _, r = flash.dropout_threshold(dropout_p)
+        seed = flash.draw_seed() if seed is None else seed
+        keep = flash.dropout_keep(seed, B, H, T, dropout_p, q.device)
+        p = torch.where(keep, p * r, torch.zeros((), device=q.device))
     return torch.matmul(p, v.float()).to(q.dtype)
 
 
-def _attention_core(q, k, v, causal: bool, window=None, kv_lo=None) -> torch.Tensor:
+def _attention_core(q, k, v, causal: bool, window=None, kv_lo=None,
+                    dropout_p: float = 0.0, seed=None) -> torch.Tensor:
     from saturn_amd.ops import flash  # local import: optional kernel
 
     if q.is_cuda:
         return flash.flash_attention(q, k, v, causal=causal, window=window,
-                                     kv_lo=kv_lo)
+                                     kv_lo=kv_lo, dropout_p=dropout_p,
+                                     seed=seed)
+    dropout_p = flash.check_dropout(dropout_p, window, kv_lo)
     if k.shape[1] != q.shape[1]:
         rep = q.shape[1] // k.shape[1]
         k = k.repeat_interleave(rep, dim=1)
         v = v.repeat_interleave(rep, dim=1)
     lo = flash.resolve_lo(q.shape[-2], q.device, causal, window, kv_lo)
-    return attention_math(q, k, v, causal=causal, kv_lo=lo)
+    return attention_math(q, k, v, causal=causal, kv_lo=lo,
+                          dropout_p=dropout_p, seed=seed)
 
 
-def _attention(q, k, v, causal: bool, window=None, kv_lo=None) -> torch.Tensor:
+def _attention(q, k, v, causal: bool, window=None, kv_lo=None,
+               dropout_p: float = 0.0, seed=None) -> torch.Tensor:
     from saturn_amd.parallel.sequence import sp_attention, sp_world
 
     if sp_world() > 1:
@@ -287,11 +307,13 @@ def _attention(q, k, v, causal: bool, window=None, kv_lo=None) -> torch.Tensor:
         # the window bound is built there, from the gathered length)
         return sp_attention(
             q, k, v,
-            lambda a, b, c: _attention_core(a, b, c, causal, window, kv_lo))
-    return _attention_core(q, k, v, causal, window, kv_lo)
+            lambda a, b, c: _attention_core(a, b, c, causal, window, kv_lo,
+                                            dropout_p, seed))
+    return _attention_core(q, k, v, causal, window, kv_lo, dropout_p, seed)
 
 
-def causal_attention(q, k, v, window=None, kv_lo=None) -> torch.Tensor:
+def causal_attention(q, k, v, window=None, kv_lo=None,
+                     dropout_p: float = 0.0, seed=None) -> torch.Tensor:
     """Dispatch: fused CDNA4 flash kernel on GPU (when built), math path on
     CPU.  Handles GQA (k/v with fewer heads) by expansion.
 
@@ -299,13 +321,17 @@ def causal_attention(q, k, v, window=None, kv_lo=None) -> torch.Tensor:
     in ``flash.flash_attention``.  Under Ulysses sequence parallelism the
     bound applies to the gathered sequence: ``window`` works unchanged, and
     an explicit ``kv_lo`` must be the FULL-sequence bound ([T_full] or
-    [B, T_full]), not the local shard's."""
-    return _attention(q, k, v, causal=True, window=window, kv_lo=kv_lo)
+    [B, T_full]), not the local shard's.
+
+    ``dropout_p`` / ``seed``: attention dropout, as in
+    ``flash.flash_attention`` (not together with ``window`` / ``kv_lo``)."""
+    return _attention(q, k, v, causal=True, window=window, kv_lo=kv_lo,
+                      dropout_p=dropout_p, seed=seed)
 
 
-def full_attention(q, k, v) -> torch.Tensor:
+def full_attention(q, k, v, dropout_p: float = 0.0, seed=None) -> torch.Tensor:
     """Bidirectional (encoder) attention — BERT/ViT."""
-    return _attention(q, k, v, causal=False)
+    return _attention(q, k, v, causal=False, dropout_p=dropout_p, seed=seed)
 
 
 # ---------------------------------------------------------------------------
