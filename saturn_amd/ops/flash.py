@@ -199,11 +199,9 @@ class _FlashFn(torch.autograd.Function):
             # kv_len and padded q rows are sliced off below (their zero
             # dO rows contribute exactly 0 to dK/dV in backward)
             q, k, v = _pad_t64(q), _pad_t64(k), _pad_t64(v)
-        if dropout_p > 0.0:
-            o, lse = ext.attn_fwd(q, k, v, causal, T, dropout_p=dropout_p,
-                                  seed=seed)
-        else:
-            o, lse = ext.attn_fwd(q, k, v, causal, T, kv_lo=kv_lo)
+        # the variant is chosen in attn_plan from kv_lo and dropout_p > 0
+        o, lse = ext.attn_fwd(q, k, v, causal, T, kv_lo=kv_lo,
+                              dropout_p=dropout_p, seed=seed)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.drop = (dropout_p, seed)  # the backward regenerates the mask
         ctx.kv_lo = kv_lo  # int32, no gradient
@@ -218,12 +216,8 @@ class _FlashFn(torch.autograd.Function):
         T = ctx.t_real
         do = _pad_t64(_dense_rows(do)) if T % 64 else _dense_rows(do)
         p, seed = ctx.drop
-        if p > 0.0:
-            dq, dk, dv = ext.attn_bwd(do, q, k, v, o, lse, ctx.causal, T,
-                                      dropout_p=p, seed=seed)
-        else:
-            dq, dk, dv = ext.attn_bwd(do, q, k, v, o, lse, ctx.causal, T,
-                                      kv_lo=ctx.kv_lo)
+        dq, dk, dv = ext.attn_bwd(do, q, k, v, o, lse, ctx.causal, T,
+                                  kv_lo=ctx.kv_lo, dropout_p=p, seed=seed)
         if T % 64:
             dq, dk, dv = dq[:, :, :T], dk[:, :, :T], dv[:, :, :T]
         return dq, dk, dv, None, None, None, None
@@ -284,19 +278,11 @@ def flash_attention(q, k, v, causal: bool = True, window=None,
     require_ext()
     if p > 0.0 and seed is None:
         seed = draw_seed()
-    if _kernel_supported(q) and p > 0.0:
-        return _FlashFn.apply(
-            _dense_rows(q), _dense_rows(k), _dense_rows(v), causal, None,
-            p, _i64(int(seed))
-        )
     if _kernel_supported(q):
         # GQA is native in the kernels: kv may keep fewer heads
-        if lo is None:
-            return _FlashFn.apply(
-                _dense_rows(q), _dense_rows(k), _dense_rows(v), causal
-            )
         return _FlashFn.apply(
-            _dense_rows(q), _dense_rows(k), _dense_rows(v), causal, lo
+            _dense_rows(q), _dense_rows(k), _dense_rows(v), causal, lo,
+            p, _i64(int(seed)) if p > 0.0 else 0
         )
     global _warned
     if not _warned:

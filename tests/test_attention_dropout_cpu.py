@@ -1,7 +1,7 @@
 """Attention dropout without a GPU: the keep function's twin
 (saturn_amd.ops.flash.dropout_keep), the math path, the reference and floor
-of tests/attn_dropout_ref.py with its mutation check, the models' attn_pdrop
-and the refusals.
+of tests/attn_ref.py under a keep mask with its mutation check, the models'
+attn_pdrop and the refusals.
 """
 
 import math
@@ -13,7 +13,6 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import attn_ref as ar  # noqa: E402
-import attn_dropout_ref as dr  # noqa: E402
 
 from saturn_amd.ops import flash  # noqa: E402
 from saturn_amd.ops.functional import (  # noqa: E402
@@ -105,21 +104,27 @@ def test_threshold():
 
 
 # ---------------------------------------------------------------------------
-# the reference and the floor reduce to attn_ref's, exactly
+# keep=None skips the mask's operations, an all-true mask with r = 1 runs
+# them: neutral arguments must not change a bit of the truth or the floor
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("causal", [True, False])
 def test_all_true_mask_is_the_plain_reference(causal):
     q, k, v, do = ar.make_inputs("randn", 1, 4, 2, 96, 64, seed=3)
-    ones = torch.ones(1, 4, 96, 96, dtype=torch.bool)
-    for a, b in zip(dr.ref64_drop(q, k, v, causal, ones, 1.0, do),
-                    ar.ref64(q, k, v, causal, do)):
-        assert torch.equal(a, b)
-    for a, b in zip(dr.base_bf16_drop(q, k, v, causal, ones, 1.0, do),
-                    ar.base_bf16(q, k, v, causal, do)):
-        assert torch.equal(a, b)
-    for a, b in zip(dr.base_bf16_drop(q, k, v, causal, ones, 1.0, do, kv_len=90),
-                    ar.base_bf16(q, k, v, causal, do, kv_len=90)):
-        assert torch.equal(a, b)
+    ones = {"keep": torch.ones(1, 4, 96, 96, dtype=torch.bool), "r": 1.0}
+    pairs = [(ar.ref64(q, k, v, causal, do, **ones),
+              ar.ref64(q, k, v, causal, do)),
+             (ar.base_bf16(q, k, v, causal, do, **ones),
+              ar.base_bf16(q, k, v, causal, do)),
+             (ar.base_bf16(q, k, v, causal, do, kv_len=90, **ones),
+              ar.base_bf16(q, k, v, causal, do, kv_len=90))]
+    if causal:      # and all three neutral arguments at once
+        zero = torch.zeros(96, dtype=torch.int32)
+        pairs += [(ar.ref64(q, k, v, True, do, lo=zero, **ones), pairs[0][1]),
+                  (ar.base_bf16(q, k, v, True, do, lo=zero, **ones), pairs[1][1])]
+    for got, plain in pairs:
+        assert len(got) == len(plain) == 5
+        for name, a, b in zip(ar.NAMES, got, plain):
+            assert a.dtype == b.dtype and torch.equal(a, b), name
 
 
 # ---------------------------------------------------------------------------
@@ -130,8 +135,8 @@ def test_all_true_mask_is_the_plain_reference(causal):
 def test_attention_math_matches_ref64_drop(causal, p):
     B, H, T, D = 2, 3, 70, 32
     q, k, v, do = (t.float() for t in ar.make_inputs("randn", B, H, H, T, D, seed=5))
-    keep, r = dr.keep_r(991, B, H, T, p)
-    ref = dr.ref64_drop(q, k, v, causal, keep, r, do)
+    keep, r = ar.keep_r(991, B, H, T, p)
+    ref = ar.ref64(q, k, v, causal, do, keep=keep, r=r)
     ql, kl, vl = (t.clone().requires_grad_(True) for t in (q, k, v))
     out = attention_math(ql, kl, vl, causal=causal, dropout_p=p, seed=991)
     out.backward(do)
@@ -172,7 +177,7 @@ def test_public_cpu_routes_share_the_mask_and_draw_seeds():
 # ---------------------------------------------------------------------------
 # 3. mutation check at the GPU matrix's shapes
 # ---------------------------------------------------------------------------
-MUT_SHAPES = sorted({(D, T, causal) for D, T, causal, _, _ in dr.MATRIX})
+MUT_SHAPES = sorted({(D, T, causal) for D, T, causal, _, _ in ar.MATRIX_DROP})
 
 
 @pytest.mark.parametrize("D,T,causal", MUT_SHAPES,
@@ -181,18 +186,19 @@ def test_mutants_are_rejected(D, T, causal):
     """Each planted bug must fail `close` (factor 2 over the floor) on every
     tensor the table names, at every shape of the GPU matrix and at the
     smaller of its two rates (fewer dropped entries: the harder case)."""
-    c = dr.case("randn", *dr.BH, dr.BH[1], T, D, causal, 0.1)
+    c = ar.case("randn", *ar.BH_DROP, ar.BH_DROP[1], T, D, causal, p=0.1,
+                seed=ar.DROP_INPUT_SEED)
     q, k, v, do, keep, r = (c[n] for n in ("q", "k", "v", "do", "keep", "r"))
-    keep2, _ = dr.keep_r(c["seed"] + 1, *dr.BH, T, 0.1)
+    keep2, _ = ar.keep_r(c["seed"] + 1, *ar.BH_DROP, T, 0.1)
     # the unmutated floor passes its own criterion trivially (ratio 1)
-    for i, name in enumerate(dr.NAMES):
+    for i, name in enumerate(ar.NAMES):
         if name != "lse":
             assert ar.close(c["base"][i], c["ref"][i], c["base"][i])
-    for kind, tensors in dr.MUTANTS.items():
+    for kind, tensors in ar.MUTANTS.items():
         mut = (kind, keep2) if kind == "bwd_seed" else (kind,)
-        got = dr.base_bf16_drop(q, k, v, causal, keep, r, do, mut=mut)
+        got = ar.base_bf16(q, k, v, causal, do, keep=keep, r=r, mut=mut)
         for name in tensors:
-            i = dr.NAMES.index(name)
+            i = ar.NAMES.index(name)
             info = ar.close_info(got[i], c["ref"][i], c["base"][i])
             assert not info["ok"], (kind, name, info)
 

@@ -1,7 +1,7 @@
 """Attention dropout fused into the K2 kernels (attention.hip's DROP
 instantiations) on the GPU: the mask read out exactly from the forward and
 from the dK/dV kernel, numerics against the fp64 reference of
-tests/attn_dropout_ref.py under attn_ref's `close` criterion, and the bitwise
+tests/attn_ref.py under its `close` criterion, and the bitwise
 properties a counter-based mask must have.
 
 Every shape has B*H <= 8 and T <= 512.  Each comparison prints an
@@ -11,7 +11,6 @@ error floor, per tensor); docs/kernels.md tabulates the worst per group.
 
 import json
 import os
-import subprocess
 import sys
 
 import pytest
@@ -19,19 +18,21 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import attn_ref as ar  # noqa: E402
-import attn_dropout_ref as dr  # noqa: E402
+import attn_run as run  # noqa: E402
 
 from saturn_amd.ops import flash  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-SEED = dr.SEED
+SEED = ar.SEED
 
 
-def _ext():
-    from saturn_amd.ops import require_ext
+def _case(kind, B, H, Hkv, T, D, causal, p):
+    return ar.case(kind, B, H, Hkv, T, D, causal, p=p, seed=ar.DROP_INPUT_SEED)
 
-    return require_ext()
+
+def _direct(q, k, v, causal, do, p, seed):
+    return run.kernel_direct(q, k, v, causal, do, p=p, seed=seed)
 
 
 def _drop_paths(T, D):
@@ -46,14 +47,9 @@ def _check(group, name, c, gqa=False):
     """Both routes for a case; they must agree bit for bit (dk/dv under GQA
     excepted: fp32 atomics in arrival order); the public four and the direct
     LSE are checked."""
-    direct, public = dr.run_case(c, DEV)
-    assert dr.bits_equal(public[0], direct[0]), "out: routes differ"
-    assert dr.bits_equal(public[1], direct[2]), "dq: routes differ"
-    if not gqa:
-        assert dr.bits_equal(public[2], direct[3]), "dk: routes differ"
-        assert dr.bits_equal(public[3], direct[4]), "dv: routes differ"
+    direct, public = run.both_routes(c, gqa)
     got = (public[0], direct[1]) + public[1:]
-    rep, bad = dr.check_case_drop(got, c)
+    rep, bad = ar.check_case(got, c["ref"], c["base"], c["lse_tol"])
     print("ATTN_RATIO", f"dropout-{group}", name, json.dumps(ar.ratios(rep)),
           "lse", json.dumps(rep.get("lse")))
     assert not bad, bad
@@ -94,17 +90,17 @@ def _packed(keep, T, D, over_rows):
 def test_forward_mask_readout(T, D, variant, causal, p):
     """q = 0 makes every seen probability 1/l exactly, so out * l / r is the
     integer whose bits are the keep flags: the forward's mask, bit for bit."""
-    path = _ext().attn_dispatch(T, D, has_drop=True)
+    path = run.ext().attn_dispatch(T, D, has_drop=True)
     assert path == _drop_paths(T, D)
     assert path.startswith(f"{variant}<{D},0,1>")
-    assert ",1>" not in _ext().attn_dispatch(T, D).split()[0]
+    assert ",1>" not in run.ext().attn_dispatch(T, D).split()[0]
     q = torch.zeros(RB, RH, T, D, dtype=torch.bfloat16, device=DEV)
     k = torch.randn(RB, RH, T, D, generator=torch.Generator().manual_seed(T + D)
                     ).bfloat16().to(DEV)
     v = _basis(T, D).to(DEV)
-    o, lse = ar.launch_guard(_ext().attn_fwd)(q, k, v, causal, T,
-                                              dropout_p=p, seed=SEED)
-    keep, r = dr.keep_r(SEED, RB, RH, T, p)
+    o, lse = run.launch_guard(run.ext().attn_fwd)(q, k, v, causal, T,
+                                                  dropout_p=p, seed=SEED)
+    keep, r = ar.keep_r(SEED, RB, RH, T, p)
     i = torch.arange(T)
     if causal:
         keep = keep & (i[None, :] <= i[:, None])
@@ -131,14 +127,14 @@ def test_dkdv_mask_readout(T, D, variant, p):
     v = _basis(T, D).to(DEV)
     do = _basis(T, D).to(DEV)
 
-    @ar.launch_guard
-    def run():
-        o, lse = _ext().attn_fwd(q, k, v, False, T, dropout_p=p, seed=SEED)
-        return _ext().attn_bwd(do, q, k, v, o, lse, False, T, dropout_p=p,
-                               seed=SEED)
+    @run.launch_guard
+    def launch():
+        o, lse = run.ext().attn_fwd(q, k, v, False, T, dropout_p=p, seed=SEED)
+        return run.ext().attn_bwd(do, q, k, v, o, lse, False, T,
+                                  dropout_p=p, seed=SEED)
 
-    dq, dk, dv = run()
-    keep, r = dr.keep_r(SEED, RB, RH, T, p)
+    dq, dk, dv = launch()
+    keep, r = ar.keep_r(SEED, RB, RH, T, p)
     pb = torch.tensor(1.0 / T).bfloat16().float().item()   # the kernel's bf16 P
     got = torch.round(dv.float().cpu() / (r * pb))
     want = _packed(keep, T, D, over_rows=True)
@@ -150,11 +146,11 @@ def test_dkdv_mask_readout(T, D, variant, p):
 # C. numerics: D x T x mask x input kind x p
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize(
-    "D,T,causal,kind,p", dr.MATRIX,
-    ids=[f"D{d}-T{t}-{'c' if c else 'n'}-{k}-p{p}" for d, t, c, k, p in dr.MATRIX])
+    "D,T,causal,kind,p", ar.MATRIX_DROP,
+    ids=[f"D{d}-T{t}-{'c' if c else 'n'}-{k}-p{p}" for d, t, c, k, p in ar.MATRIX_DROP])
 def test_matrix(D, T, causal, kind, p):
-    assert _ext().attn_dispatch(T, D, has_drop=True) == _drop_paths(T, D)
-    c = dr.case(kind, *dr.BH, dr.BH[1], T, D, causal, p)
+    assert run.ext().attn_dispatch(T, D, has_drop=True) == _drop_paths(T, D)
+    c = _case(kind, *ar.BH_DROP, ar.BH_DROP[1], T, D, causal, p)
     _check("C", f"D{D}-T{T}-{'c' if causal else 'n'}-{kind}-p{p}", c)
 
 
@@ -165,14 +161,14 @@ def test_matrix(D, T, causal, kind, p):
 @pytest.mark.parametrize("D", [64, 256])
 @pytest.mark.parametrize("causal", [True, False], ids=["causal", "full"])
 def test_ragged_T(D, T, causal):
-    c = dr.case("randn", *dr.BH, dr.BH[1], T, D, causal, 0.1)
+    c = _case("randn", *ar.BH_DROP, ar.BH_DROP[1], T, D, causal, 0.1)
     got = _check("D", f"D{D}-T{T}-{'c' if causal else 'n'}", c)
     # the mask is the padded call's: the same rows through ext on inputs
     # padded by hand give the same bits
     q, k, v = (flash._pad_t64(c[n].to(DEV)) for n in ("q", "k", "v"))
-    o, _ = ar.launch_guard(_ext().attn_fwd)(q, k, v, causal, T, dropout_p=0.1,
-                                            seed=c["seed"])
-    assert dr.bits_equal(o[:, :, :T].contiguous(), got[0].contiguous())
+    o, _ = run.launch_guard(run.ext().attn_fwd)(
+        q, k, v, causal, T, dropout_p=0.1, seed=c["seed"])
+    assert run.bits_equal(o[:, :, :T].contiguous(), got[0].contiguous())
 
 
 # ---------------------------------------------------------------------------
@@ -181,47 +177,47 @@ def test_ragged_T(D, T, causal):
 @pytest.mark.parametrize("H,Hkv", [(8, 2), (4, 1)])
 @pytest.mark.parametrize("D", [64, 128])
 def test_gqa(D, H, Hkv):
-    c = dr.case("randn", 1, H, Hkv, 192, D, True, 0.1)
+    c = _case("randn", 1, H, Hkv, 192, D, True, 0.1)
     _check("E", f"D{D}-H{H}kv{Hkv}", c, gqa=True)
 
 
 # ---------------------------------------------------------------------------
 # F. bitwise properties
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("D", dr.DS)
+@pytest.mark.parametrize("D", ar.DS)
 def test_run_to_run_bitwise(D):
-    c = dr.case("randn", *dr.BH, dr.BH[1], 256, D, True, 0.1)
-    a, _ = dr.run_case(c, DEV)
-    b, _ = dr.run_case(c, DEV)
+    c = _case("randn", *ar.BH_DROP, ar.BH_DROP[1], 256, D, True, 0.1)
+    a, _ = run.both_routes(c)
+    b, _ = run.both_routes(c)
     for name, x, y in zip(ar.NAMES, a, b):
-        assert dr.bits_equal(x, y), name
+        assert run.bits_equal(x, y), name
     # another seed is another mask
     q, k, v, do = (c[n].to(DEV) for n in ("q", "k", "v", "do"))
-    other = dr.kernel_direct_drop(q, k, v, True, do, 0.1, c["seed"] + 1)
-    assert not dr.bits_equal(other[0], a[0])
-    assert dr.bits_equal(other[1], a[1])          # LSE does not see the mask
+    other = _direct(q, k, v, True, do, 0.1, c["seed"] + 1)
+    assert not run.bits_equal(other[0], a[0])
+    assert run.bits_equal(other[1], a[1])          # LSE does not see the mask
 
 
 @pytest.mark.parametrize("T", [192, 256])
-@pytest.mark.parametrize("D", dr.DS)
+@pytest.mark.parametrize("D", ar.DS)
 def test_p0_is_the_plain_call(D, T):
     q, k, v, do = ar.make_inputs("randn", 1, 2, 2, T, D, DEV, seed=4)
-    plain = ar.kernel_public(q, k, v, True, do)
+    plain = run.kernel_public(q, k, v, True, do)
 
-    @ar.launch_guard
-    def run():
+    @run.launch_guard
+    def launch():
         ql, kl, vl = (t.detach().clone().requires_grad_(True) for t in (q, k, v))
         out = flash.flash_attention(ql, kl, vl, causal=True, dropout_p=0.0,
                                     seed=12345)
         out.backward(do)
         return out.detach(), ql.grad, kl.grad, vl.grad
 
-    for x, y in zip(plain, run()):
-        assert dr.bits_equal(x, y)
+    for x, y in zip(plain, launch()):
+        assert run.bits_equal(x, y)
     # thr == 0 through ext launches the plain instantiations too
-    o, lse = ar.launch_guard(_ext().attn_fwd)(q, k, v, True, T,
-                                              dropout_p=2.0 ** -18, seed=7)
-    assert dr.bits_equal(o.contiguous(), plain[0].contiguous())
+    o, lse = run.launch_guard(run.ext().attn_fwd)(q, k, v, True, T,
+                                                  dropout_p=2.0 ** -18, seed=7)
+    assert run.bits_equal(o.contiguous(), plain[0].contiguous())
 
 
 @pytest.mark.parametrize("D", [64, 128])
@@ -229,15 +225,15 @@ def test_head_isolation_bitwise(D):
     """Replacing one head's inputs leaves every other (b, h) bit for bit."""
     B, H, T = 2, 3, 128
     q, k, v, do = ar.make_inputs("randn", B, H, H, T, D, DEV, seed=5)
-    a = dr.kernel_direct_drop(q, k, v, True, do, 0.5, SEED)
+    a = _direct(q, k, v, True, do, 0.5, SEED)
     q2, k2, v2, do2 = (t.clone() for t in (q, k, v, do))
     for t in (q2, k2, v2, do2):
         t[1, 1] = torch.randn(T, D, device=DEV).bfloat16()
-    b = dr.kernel_direct_drop(q2, k2, v2, True, do2, 0.5, SEED)
+    b = _direct(q2, k2, v2, True, do2, 0.5, SEED)
     for name, x, y in zip(ar.NAMES, a, b):
         for bb in range(B):
             for hh in range(H):
-                same = dr.bits_equal(x[bb, hh], y[bb, hh])
+                same = run.bits_equal(x[bb, hh], y[bb, hh])
                 assert same == ((bb, hh) != (1, 1)), (name, bb, hh)
 
 
@@ -250,7 +246,7 @@ def test_all_dropped_rows_and_never_kept_keys():
     denominator, dS = -P delta scale there, and the comparison with
     ref64_drop below covers it."""
     B, H, T, D, p = 2, 3, 64, 64, 0.9
-    c = dr.case("randn", B, H, H, T, D, True, p)
+    c = _case("randn", B, H, H, T, D, True, p)
     out, lse, dq, dk, dv = _check("F", "p0.9-T64", c)
     i = torch.arange(T)
     seen = c["keep"] & (i[None, :] <= i[:, None])
@@ -270,7 +266,7 @@ def test_all_dropped_rows_and_never_kept_keys():
 # ---------------------------------------------------------------------------
 def test_refusals():
     q, k, v, do = ar.make_inputs("randn", 1, 2, 2, 64, 64, DEV, seed=1)
-    ext = _ext()
+    ext = run.ext()
     lo = torch.zeros(64, dtype=torch.int32, device=DEV)
     with pytest.raises(RuntimeError, match="dropout_p"):
         ext.attn_fwd(q, k, v, True, 64, dropout_p=1.0, seed=1)
@@ -292,60 +288,22 @@ def test_refusals():
     torch.cuda.synchronize()
 
 
-# child time limit, by the rule of the switch children of
-# test_attention_gpu.py: START_UP_S + FACTOR x the same work measured in
-# this process (interpreter + torch import + device start-up and code-object
-# load on a shared machine, then the work with 10x headroom)
-START_UP_S = 120.0
-FACTOR = 10.0
-SWITCHES = ("SAMD_ATTN_V2", "SAMD_ATTN_BWD_TR16", "SAMD_ATTN_BWD_VL2",
-            "SAMD_ATTN_DQ_GKV")
-_state = {"seconds": None, "child_died": False}
-
-
 def _own_seconds():
-    if _state["seconds"] is None:
-        dr.child_matrix(DEV)                          # warm
-        res = dr.child_matrix(DEV)
-        assert not res["failures"], res["failures"]
-        assert res["path"] == _drop_paths(256, 128)
-        _state["seconds"] = res["seconds"]
-    return _state["seconds"]
-
-
-def _child(mode, setting):
-    if _state["child_died"]:
-        pytest.skip("an earlier child ended by signal, abort or timeout: no "
-                    "further child is started")
-    if ar.device_error:
-        pytest.fail("not started: device error earlier in this process: "
-                    + ar.device_error[0])
-    limit = START_UP_S + FACTOR * _own_seconds()
-    env = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-    env.update(setting)
-    cmd = [sys.executable, os.path.abspath(dr.__file__), "--child", mode]
-    try:
-        p = subprocess.run(cmd, env=env, timeout=limit, capture_output=True,
-                           text=True)
-    except subprocess.TimeoutExpired:
-        _state["child_died"] = True
-        pytest.fail(f"{setting}: child exceeded its {limit:.0f} s limit")
-    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
-    if (p.returncode != 0 or not lines or "HIP error" in p.stderr
-            or "hipError" in p.stderr):
-        _state["child_died"] = True
-        pytest.fail(f"{setting}: child status {p.returncode}\n{p.stderr[-2000:]}")
-    return json.loads(lines[-1])
+    res = run.own_run("drop-matrix")
+    assert res["path"] == _drop_paths(256, 128)
+    return res["seconds"]
 
 
 def test_child_vl2_is_refused_by_name():
-    res = _child("refuse", {"SAMD_ATTN_BWD_VL2": "1"})
+    res, _, _ = run.run_child("drop-refuse", {"SAMD_ATTN_BWD_VL2": "1"},
+                               _own_seconds())
     assert res["refused"], res
     assert "SAMD_ATTN_BWD_VL2" in res["message"], res
 
 
 def test_child_v2_off_takes_v1():
-    res = _child("matrix", {"SAMD_ATTN_V2": "0"})
+    res, _, _ = run.run_child("drop-matrix", {"SAMD_ATTN_V2": "0"},
+                               _own_seconds())
     print("ATTN_DROPOUT_CHILD SAMD_ATTN_V2=0", json.dumps(res))
     assert res["path"].startswith("attn_fwd_kernel<128,0,1>"), res["path"]
     assert not res["failures"], res["failures"]

@@ -4,8 +4,8 @@ Every dispatch path, mask edge and layout of attn_fwd / attn_bwd against the
 fp64 reference of tests/attn_ref.py under its `close` criterion (tolerance
 measured on the bf16 reference composition, never on the kernel), the LSE
 criterion, exact bitwise properties, analytic q = 0 results and one child
-process per environment switch.  Shapes are the smallest that reach the code
-in question: B*H <= 15, T <= 512.
+process per environment switch (tests/attn_run.py).  Shapes are the smallest
+that reach the code in question: B*H <= 15, T <= 512.
 
 Each comparison prints an ``ATTN_RATIO <group> <case> <json>`` line (kernel
 error over the error floor, per tensor); docs/kernels.md tabulates the worst
@@ -16,34 +16,18 @@ import json
 import math
 import os
 import re
-import subprocess
 import sys
 
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import attn_ref as ar  # noqa: E402  (plain helper module beside this file)
+import attn_ref as ar  # noqa: E402  (plain helper modules beside this file)
+import attn_run as run  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 DS = [64, 128, 256]
-
-
-def _ext():
-    from saturn_amd.ops import require_ext
-
-    return require_ext()
-
-
-def _bits(t):
-    t = t.contiguous()
-    return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
-
-
-def _same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and \
-        torch.equal(_bits(a), _bits(b))
 
 
 def _default_paths(T, D):
@@ -60,7 +44,7 @@ def _check(group, case, got, q, k, v, causal, do, skip=(), every_head=True):
     """every_head: the LSE tolerance must lie below the one-key shift on
     every (b, h), so a mask fault confined to one head is seen too; only the
     peaky inputs (edge key ~1e-6 of a row on some heads) settle for one."""
-    rep, bad = ar.check_case(got, q, k, v, causal, do, every_head=every_head)
+    rep, bad = ar.check_plain(got, q, k, v, causal, do, every_head=every_head)
     print("ATTN_RATIO", group, case, json.dumps(ar.ratios(rep)),
           "lse", json.dumps(rep.get("lse")))
     bad = [b for b in bad if b.split(":")[0] not in skip]
@@ -69,17 +53,10 @@ def _check(group, case, got, q, k, v, causal, do, skip=(), every_head=True):
 
 
 def _both(q, k, v, causal, do, gqa=False):
-    """Public wrapper for out and the gradients (shape and leaf plumbing),
-    direct calls for LSE; the two routes must agree bit for bit, except for
-    dk/dv under GQA, which are summed with fp32 atomics in arrival order."""
-    out, dq, dk, dv = ar.kernel_public(q, k, v, causal, do)
-    assert out.shape == q.shape and dq.shape == q.shape
-    assert dk.shape == k.shape and dv.shape == v.shape
-    d = ar.kernel_direct(q, k, v, causal, do)
-    assert _same(out, d[0]) and _same(dq, d[2])
-    if not gqa:
-        assert _same(dk, d[3]) and _same(dv, d[4])
-    return out, d[1], dq, dk, dv
+    """run.both_routes: the public wrapper's out and gradients with the
+    direct route's LSE."""
+    direct, public = run.both_routes((q, k, v, causal, do), gqa)
+    return (public[0], direct[1]) + public[1:]
 
 
 # ---------------------------------------------------------------------------
@@ -100,9 +77,9 @@ def test_path_matrix(D, T, path, causal, B, H, kind):
     want = _default_paths(T, D)
     assert want.startswith("attn_fwd_v2_kernel" if path == "v2"
                            else "attn_fwd_kernel<")
-    assert _ext().attn_dispatch(T, D) == want
+    assert run.ext().attn_dispatch(T, D) == want
     q, k, v, do = ar.make_inputs(kind, B, H, H, T, D, DEV, seed=1)
-    got = ar.kernel_direct(q, k, v, causal, do)
+    got = run.kernel_direct(q, k, v, causal, do)
     _check("A", f"D{D}T{T}{'c' if causal else 'n'}B{B}H{H}{kind}",
            got, q, k, v, causal, do, every_head=(kind != "peaky"))
 
@@ -116,7 +93,8 @@ def test_path_matrix(D, T, path, causal, B, H, kind):
 def test_ragged_T(D, T, causal):
     """130 -> 192 and 257 -> 320 are the v1 forward with kv_len < T."""
     B, H = 2, 3
-    assert _ext().attn_dispatch(ar.padded_t(T), D) == _default_paths(ar.padded_t(T), D)
+    Tp = ar.padded_t(T)
+    assert run.ext().attn_dispatch(Tp, D) == _default_paths(Tp, D)
     q, k, v, do = ar.make_inputs("randn", B, H, H, T, D, DEV, seed=2)
     got = _both(q, k, v, causal, do)
     if T > 1:
@@ -134,7 +112,7 @@ def test_ragged_T(D, T, causal):
           * (do.double() * v.double()).abs().sum(-1).max().item())
     assert got[2].abs().max().item() <= 1.02 * ds * k.abs().max().item()
     assert got[3].abs().max().item() <= 1.02 * ds * q.abs().max().item()
-    assert _same(got[0], v) and _same(got[4], do)   # p = 1 exactly
+    assert run.bits_equal(got[0], v) and run.bits_equal(got[4], do)   # p = 1 exactly
 
 
 # ---------------------------------------------------------------------------
@@ -168,24 +146,24 @@ def _fresh(like, seed):
 @pytest.mark.parametrize("D", DS)
 def test_causality_bitwise(D, T, t0):
     q, k, v, do = ar.make_inputs("randn", 1, 3, 3, T, D, DEV, seed=4)
-    o, lse, dq, dk, dv = ar.kernel_direct(q, k, v, True, do)
+    o, lse, dq, dk, dv = run.kernel_direct(q, k, v, True, do)
     # the future cannot reach the past
     k2, v2 = k.clone(), v.clone()
     k2[:, :, t0:] = _fresh(k[:, :, t0:], 41)
     v2[:, :, t0:] = _fresh(v[:, :, t0:], 42)
-    o2, lse2, dq2, _, _ = ar.kernel_direct(q, k2, v2, True, do)
-    assert _same(o[:, :, :t0], o2[:, :, :t0])
-    assert _same(lse[:, :, :t0], lse2[:, :, :t0])
-    assert _same(dq[:, :, :t0], dq2[:, :, :t0])
-    assert not _same(o[:, :, t0:], o2[:, :, t0:])    # the change was seen
+    o2, lse2, dq2, _, _ = run.kernel_direct(q, k2, v2, True, do)
+    assert run.bits_equal(o[:, :, :t0], o2[:, :, :t0])
+    assert run.bits_equal(lse[:, :, :t0], lse2[:, :, :t0])
+    assert run.bits_equal(dq[:, :, :t0], dq2[:, :, :t0])
+    assert not run.bits_equal(o[:, :, t0:], o2[:, :, t0:])    # the change was seen
     # earlier queries cannot reach later keys
     q3, do3 = q.clone(), do.clone()
     q3[:, :, :t0] = _fresh(q[:, :, :t0], 43)
     do3[:, :, :t0] = _fresh(do[:, :, :t0], 44)
-    _, _, _, dk3, dv3 = ar.kernel_direct(q3, k, v, True, do3)
-    assert _same(dk[:, :, t0:], dk3[:, :, t0:])
-    assert _same(dv[:, :, t0:], dv3[:, :, t0:])
-    assert not _same(dk[:, :, :t0], dk3[:, :, :t0])
+    _, _, _, dk3, dv3 = run.kernel_direct(q3, k, v, True, do3)
+    assert run.bits_equal(dk[:, :, t0:], dk3[:, :, t0:])
+    assert run.bits_equal(dv[:, :, t0:], dv3[:, :, t0:])
+    assert not run.bits_equal(dk[:, :, :t0], dk3[:, :, :t0])
 
 
 @pytest.mark.parametrize("causal", [True, False])
@@ -206,11 +184,11 @@ def test_kv_len_masking_bitwise(D, kv_len, causal):
         if zero_pad:
             k2[:, :, kv_len:] = 0
             v2[:, :, kv_len:] = 0
-        o, lse, dq, dk, dv = ar.ext_fwd_bwd(q, k2, v2, causal, do, kv_len)
+        o, lse, dq, dk, dv = run.ext_fwd_bwd(q, k2, v2, causal, do, kv_len)
         assert (dk[:, :, kv_len:] == 0).all() and (dv[:, :, kv_len:] == 0).all()
         res.append(tuple(t[:, :, :kv_len] for t in (o, lse, dq, dk, dv)))
     for a, b in zip(*res):
-        assert _same(a, b)
+        assert run.bits_equal(a, b)
     n = kv_len
     _check("D", f"D{D}kv{kv_len}{'c' if causal else 'n'}", res[1],
            q[:, :, :n], k[:, :, :n], v[:, :, :n], causal, do[:, :, :n])
@@ -221,17 +199,17 @@ def test_kv_len_masking_bitwise(D, kv_len, causal):
 def test_batch_head_isolation_bitwise(D, causal):
     B, H, T = 2, 3, 192
     q, k, v, do = ar.make_inputs("randn", B, H, H, T, D, DEV, seed=6)
-    a = ar.kernel_direct(q, k, v, causal, do)
+    a = run.kernel_direct(q, k, v, causal, do)
     q2, k2, v2, do2 = (t.clone() for t in (q, k, v, do))
     for i, t in enumerate((q2, k2, v2, do2)):
         t[1, 1] = _fresh(t[1, 1], 60 + i)
-    b = ar.kernel_direct(q2, k2, v2, causal, do2)
+    b = run.kernel_direct(q2, k2, v2, causal, do2)
     keep = torch.ones(B, H, dtype=torch.bool)
     keep[1, 1] = False
     keep = keep.to(DEV)
     for x, y in zip(a, b):
-        assert _same(x[keep], y[keep])
-        assert not _same(x[1, 1], y[1, 1])
+        assert run.bits_equal(x[keep], y[keep])
+        assert not run.bits_equal(x[1, 1], y[1, 1])
 
 
 @pytest.mark.parametrize("causal", [True, False])
@@ -241,25 +219,25 @@ def test_gqa_kv_head_isolation(D, causal):
     H, Hkv, T, j = 6, 2, 192, 1
     rep = H // Hkv
     q, k, v, do = ar.make_inputs("randn", 1, H, Hkv, T, D, DEV, seed=7)
-    o, lse, dq, _, _ = ar.kernel_direct(q, k, v, causal, do)
+    o, lse, dq, _, _ = run.kernel_direct(q, k, v, causal, do)
     k2, v2 = k.clone(), v.clone()
     k2[:, j] = _fresh(k[:, j], 71)
     v2[:, j] = _fresh(v[:, j], 72)
-    o2, lse2, dq2, _, _ = ar.kernel_direct(q, k2, v2, causal, do)
+    o2, lse2, dq2, _, _ = run.kernel_direct(q, k2, v2, causal, do)
     other = [h for h in range(H) if not j * rep <= h < (j + 1) * rep]
-    assert _same(o[:, other], o2[:, other])
-    assert _same(lse[:, other], lse2[:, other])
-    assert _same(dq[:, other], dq2[:, other])
+    assert run.bits_equal(o[:, other], o2[:, other])
+    assert run.bits_equal(lse[:, other], lse2[:, other])
+    assert run.bits_equal(dq[:, other], dq2[:, other])
 
 
 @pytest.mark.parametrize("T", [192, 256])
 @pytest.mark.parametrize("D", DS)
 def test_run_to_run_bitwise(D, T):
     q, k, v, do = ar.make_inputs("randn", 3, 5, 5, T, D, DEV, seed=8)
-    a = ar.kernel_direct(q, k, v, True, do)
-    b = ar.kernel_direct(q, k, v, True, do)
+    a = run.kernel_direct(q, k, v, True, do)
+    b = run.kernel_direct(q, k, v, True, do)
     for x, y in zip(a, b):
-        assert _same(x, y)
+        assert run.bits_equal(x, y)
 
 
 # ---------------------------------------------------------------------------
@@ -270,12 +248,12 @@ def test_run_to_run_bitwise(D, T):
 @pytest.mark.parametrize("D", DS)
 def test_q_zero_counts_keys(D, T, causal):
     q, k, v, do = ar.make_inputs("qzero", 1, 3, 3, T, D, DEV, seed=9)
-    o, lse, _, _, _ = ar.kernel_direct(q, k, v, causal, do)
+    o, lse, _, _, _ = run.kernel_direct(q, k, v, causal, do)
     n = torch.arange(1, T + 1, device=DEV, dtype=torch.float64)
     if not causal:
         n = torch.full_like(n, T)
     want_lse = torch.log(n).expand(1, 3, T)
-    tol = ar.lse_tolerance(q, k, causal, want_lse)
+    tol = ar.lse_tolerance(q, k, ar.allowed(T, causal, device=DEV), want_lse)
     one_key = math.log(T) - math.log(T - 1)      # smallest miscount, last row
     assert tol < one_key
     assert ar.max_err(lse, want_lse) <= tol
@@ -298,16 +276,16 @@ def test_layout_fused_qkv_buffer(D, T, causal):
     """q, k, v as slices of one [B, T, 3, H, D] leaf: row stride 3*H*D."""
     B, H = 2, 3
     q, k, v, do = ar.make_inputs("randn", B, H, H, T, D, DEV, seed=10)
-    ref = ar.kernel_public(q, k, v, causal, do)
+    ref = run.kernel_public(q, k, v, causal, do)
     qkv = torch.stack([t.transpose(1, 2) for t in (q, k, v)], dim=2)
     qkv = qkv.contiguous().requires_grad_(True)
     assert qkv.shape == (B, T, 3, H, D)
     qv, kv, vv = (qkv[:, :, i].transpose(1, 2) for i in range(3))
     assert qv.stride(2) == 3 * H * D and not qv.is_contiguous()
-    out = ar.flash_fwd_bwd(qv, kv, vv, causal, do)
-    assert _same(out, ref[0])
+    out = run.flash_fwd_bwd(qv, kv, vv, causal, do)
+    assert run.bits_equal(out, ref[0])
     for i in range(3):
-        assert _same(qkv.grad[:, :, i].transpose(1, 2), ref[1 + i])
+        assert run.bits_equal(qkv.grad[:, :, i].transpose(1, 2), ref[1 + i])
 
 
 @pytest.mark.parametrize("causal", [True, False])
@@ -318,14 +296,14 @@ def test_layout_gqa_transposed_kv(D, causal):
     fixed order), so they are held to `close` instead."""
     H, Hkv, T = 6, 2, 197
     q, k, v, do = ar.make_inputs("randn", 1, H, Hkv, T, D, DEV, seed=11)
-    ref = ar.kernel_public(q, k, v, causal, do)
+    ref = run.kernel_public(q, k, v, causal, do)
     kl = k.transpose(1, 2).contiguous().requires_grad_(True)   # [B,T,Hkv,D]
     vl = v.transpose(1, 2).contiguous().requires_grad_(True)
     ql = q.clone().requires_grad_(True)
-    out = ar.flash_fwd_bwd(ql, kl.transpose(1, 2), vl.transpose(1, 2),
-                           causal, do)
-    assert _same(out, ref[0]) and _same(ql.grad, ref[1])
-    lse = ar.kernel_direct(q, k, v, causal, do)[1]
+    out = run.flash_fwd_bwd(ql, kl.transpose(1, 2), vl.transpose(1, 2),
+                            causal, do)
+    assert run.bits_equal(out, ref[0]) and run.bits_equal(ql.grad, ref[1])
+    lse = run.kernel_direct(q, k, v, causal, do)[1]
     got = (out, lse, ql.grad, kl.grad.transpose(1, 2),
            vl.grad.transpose(1, 2))
     _check("F", f"D{D}gqa{'c' if causal else 'n'}", got, q, k, v, causal, do)
@@ -339,7 +317,7 @@ def test_layout_noncontiguous_dout(D, T, form):
 
     B, H = 2, 3
     q, k, v, do = ar.make_inputs("randn", B, H, H, T, D, DEV, seed=12)
-    ref = ar.kernel_public(q, k, v, True, do)
+    ref = run.kernel_public(q, k, v, True, do)
     if form == "transposed":
         do2 = do.transpose(1, 2).contiguous().transpose(1, 2)
         assert _dense_rows(do2) is do2               # addressed in place
@@ -350,9 +328,9 @@ def test_layout_noncontiguous_dout(D, T, form):
         assert do2.stride(2) % 8 != 0 and _dense_rows(do2) is not do2
     assert not do2.is_contiguous() and torch.equal(do2, do)
     ql, kl, vl = (t.clone().requires_grad_(True) for t in (q, k, v))
-    out = ar.flash_fwd_bwd(ql, kl, vl, True, do2)
+    out = run.flash_fwd_bwd(ql, kl, vl, True, do2)
     for a, b in zip((out, ql.grad, kl.grad, vl.grad), ref):
-        assert _same(a, b)
+        assert run.bits_equal(a, b)
 
 
 def _off(t, form):
@@ -382,13 +360,13 @@ def test_layout_misaligned_rows(D, form):
     with a ragged T the wrapper's padding would make fresh tensors anyway."""
     B, H, T = 2, 3, 192
     q, k, v, do = ar.make_inputs("randn", B, H, H, T, D, DEV, seed=13)
-    ref = ar.kernel_public(q, k, v, True, do)
+    ref = run.kernel_public(q, k, v, True, do)
 
     leaves = [_off(t, form).detach().requires_grad_(True) for t in (q, k, v)]
     assert all(t.data_ptr() % 16 == 8 for t in leaves)
-    out = ar.flash_fwd_bwd(*leaves, True, _off(do, form))
+    out = run.flash_fwd_bwd(*leaves, True, _off(do, form))
     for a, b in zip((out, *(t.grad for t in leaves)), ref):
-        assert _same(a, b)
+        assert run.bits_equal(a, b)
 
 
 @pytest.mark.parametrize("T", [64, 128])            # v1 / v2 forward
@@ -399,11 +377,11 @@ def test_layout_misaligned_kv_direct(D, T):
     copied).  Only q's pointer is held to 16 B; such k and v are accepted and
     give the bits of the contiguous call."""
     q, k, v, do = ar.make_inputs("randn", 1, 2, 2, T, D, DEV, seed=14)
-    ref = ar.ext_fwd_bwd(q, k, v, True, do, T)
-    got = ar.ext_fwd_bwd(q, _off(k, "column_slice"), _off(v, "column_slice"),
-                         True, do, T)
+    ref = run.ext_fwd_bwd(q, k, v, True, do, T)
+    got = run.ext_fwd_bwd(q, _off(k, "column_slice"), _off(v, "column_slice"),
+                          True, do, T)
     for a, b in zip(got, ref):
-        assert _same(a, b)
+        assert run.bits_equal(a, b)
 
 
 # ---------------------------------------------------------------------------
@@ -420,30 +398,12 @@ SETTINGS = [
     ({"SAMD_ATTN_BWD_TR16": "0", "SAMD_ATTN_BWD_VL2": "1"}, "T256_D64",
      "attn_bwd_kernel<64,0,1>"),
 ]
-SWITCH_NAMES = sorted({n for s, _, _ in SETTINGS for n in s})
-# child time limit = START_UP_S + SWEEP_FACTOR x the default-settings sweep
-# measured in this process: interpreter + torch import + device start-up and
-# code-object load on a shared machine, then the sweep with 10x headroom
-START_UP_S = 120.0
-SWEEP_FACTOR = 10.0
-_state = {"default_seconds": None, "child_died": False}
-
-
-def _default_sweep_seconds():
-    if _state["default_seconds"] is None:
-        ar.sweep(DEV)                                # warm: code objects loaded
-        res = ar.sweep(DEV)
-        assert not res["failures"], res["failures"]
-        _state["default_seconds"] = res["seconds"]
-        _state["default"] = res
-    return _state["default_seconds"]
 
 
 def test_sweep_default_settings():
-    for n in SWITCH_NAMES:
+    for n in run.SWITCHES:
         assert n not in os.environ, f"{n} is set: this suite tests the defaults"
-    _default_sweep_seconds()
-    res = _state["default"]
+    res = run.own_run("sweep")
     print("ATTN_SWEEP default", json.dumps(res))
     for key, path in res["paths"].items():
         T, D = (int(x[1:]) for x in key.split("_"))
@@ -454,40 +414,15 @@ def test_sweep_default_settings():
                          ids=["+".join(f"{k}={v}" for k, v in s.items())
                               for s, _, _ in SETTINGS])
 def test_switch_in_child_process(setting, key, expect):
-    if _state["child_died"]:
-        pytest.skip("an earlier switch child ended by signal, abort or "
-                    "timeout: no further child is started")
-    if ar.device_error:
-        pytest.fail("not started: device error earlier in this process: "
-                    + ar.device_error[0])
-    limit = START_UP_S + SWEEP_FACTOR * _default_sweep_seconds()
-    env = {k: v for k, v in os.environ.items() if k not in SWITCH_NAMES}
-    env.update(setting)
-    cmd = [sys.executable, os.path.abspath(ar.__file__), "--sweep"]
-    try:
-        p = subprocess.run(cmd, env=env, timeout=limit, capture_output=True,
-                           text=True)
-    except subprocess.TimeoutExpired:
-        _state["child_died"] = True
-        pytest.fail(f"{setting}: child exceeded its {limit:.0f} s limit")
-    if p.returncode < 0 or p.returncode == 134:
-        _state["child_died"] = True
-        pytest.fail(f"{setting}: child died with status {p.returncode}\n"
-                    f"{p.stderr[-2000:]}")
-    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
-    if not lines or "HIP error" in p.stderr or "hipError" in p.stderr:
-        # the sweep did not finish (a device error surfaces as an exception,
-        # status 1, no result line): treated like a signal, no further child
-        _state["child_died"] = True
-        pytest.fail(f"{setting}: child gave no result or hit a device error "
-                    f"(status {p.returncode})\n{p.stderr[-2000:]}")
-    res = json.loads(lines[-1])
+    assert set(setting) <= set(run.SWITCHES)
+    res, status, limit = run.run_child("sweep", setting,
+                                       run.own_run("sweep")["seconds"])
     print("ATTN_SWEEP", json.dumps(setting), f"limit {limit:.0f}s",
           json.dumps(res))
     assert expect in res["paths"][key], (expect, res["paths"][key])
     assert not res["failures"], res["failures"]
-    assert p.returncode == 0
-    assert len(res["cases"]) == 2 * len(ar.SWEEP_CASES)
+    assert status == 0
+    assert len(res["cases"]) == 2 * len(run.SWEEP_CASES)
 
 
 # ---------------------------------------------------------------------------
@@ -509,13 +444,13 @@ BAD_BWD_ARGS = [
                          ids=[f"{n}-{w}" for n, w, _ in BAD_BWD_ARGS])
 def test_bwd_refuses_bad_argument(name, what, make):
     q, k, v, do = ar.make_inputs("randn", 1, 2, 2, 64, 64, DEV, seed=15)
-    o, lse = _ext().attn_fwd(q, k, v, True, 64)
+    o, lse = run.ext().attn_fwd(q, k, v, True, 64)
     a = {"dout": do, "q": q, "k": k, "v": v, "o": o, "lse": lse}
     a[name] = make(a)
     if name == "lse":
         assert a["lse"].shape == lse.shape
     with pytest.raises(RuntimeError) as e:
-        _ext().attn_bwd(a["dout"], a["q"], a["k"], a["v"], a["o"], a["lse"],
+        run.ext().attn_bwd(a["dout"], a["q"], a["k"], a["v"], a["o"], a["lse"],
                         True, 64)
     msg = str(e.value).splitlines()[0]
     assert msg.startswith("attn_bwd:") and re.search(rf"\b{name}\b", msg), msg

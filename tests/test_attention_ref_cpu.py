@@ -64,21 +64,9 @@ def test_ulp_bf16():
 # ---------------------------------------------------------------------------
 # the floor itself meets the criterion and the LSE check is not vacuous
 # ---------------------------------------------------------------------------
-SHAPES = [
-    # (B, H, Hkv, T, D): shapes of the GPU tests' groups A, B and C
-    (1, 3, 3, 192, 64),
-    (3, 5, 5, 320, 128),
-    (1, 3, 3, 512, 256),
-    (1, 3, 3, 130, 64),
-    (1, 3, 3, 257, 128),
-    (1, 6, 2, 197, 128),
-    (1, 4, 1, 192, 64),
-]
-
-
 @pytest.mark.parametrize("kind", ["randn", "peaky"])
 @pytest.mark.parametrize("causal", [True, False])
-@pytest.mark.parametrize("B,H,Hkv,T,D", SHAPES)
+@pytest.mark.parametrize("B,H,Hkv,T,D", ar.SHAPES)
 def test_floor_passes_its_own_criterion(B, H, Hkv, T, D, causal, kind):
     """base_bf16 fed back as the 'kernel' must pass (ratio 1 by
     construction), including tolerance < one-key shift for the LSE: on
@@ -86,8 +74,8 @@ def test_floor_passes_its_own_criterion(B, H, Hkv, T, D, causal, kind):
     (their edge key weighs ~1e-6 on some heads)."""
     q, k, v, do = ar.make_inputs(kind, B, H, Hkv, T, D)
     got = ar.base_bf16(q, k, v, causal, do)
-    rep, bad = ar.check_case(got, q, k, v, causal, do,
-                             every_head=(kind != "peaky"))
+    rep, bad = ar.check_plain(got, q, k, v, causal, do,
+                              every_head=(kind != "peaky"))
     print(kind, causal, (B, H, Hkv, T, D), rep["lse"])
     assert not bad, bad
 
@@ -133,17 +121,17 @@ def _mutated(q, k, v, causal, do, mut):
 
 
 @pytest.mark.parametrize("causal", [True, False])
-@pytest.mark.parametrize("B,H,Hkv,T,D", SHAPES)
+@pytest.mark.parametrize("B,H,Hkv,T,D", ar.SHAPES)
 def test_criterion_rejects_planted_bugs(B, H, Hkv, T, D, causal):
     q, k, v, do = ar.make_inputs("randn", B, H, Hkv, T, D)
     ref = ar.ref64(q, k, v, causal, do)
     # unmutated, through the same padded route: passes
-    rep, bad = ar.check_case(_mutated(q, k, v, causal, do, None),
-                             q, k, v, causal, do, ref=ref)
+    rep, bad = ar.check_plain(_mutated(q, k, v, causal, do, None),
+                              q, k, v, causal, do, ref=ref)
     assert not bad, bad
     for mut, must in _mutations(B, H, Hkv, T, D, causal):
         got = _mutated(q, k, v, causal, do, mut)
-        rep, bad = ar.check_case(got, q, k, v, causal, do, ref=ref)
+        rep, bad = ar.check_plain(got, q, k, v, causal, do, ref=ref)
         print(mut, bad)
         for check in must:
             assert any(b.startswith(check) for b in bad), \
@@ -163,7 +151,7 @@ def test_old_norm_check_accepts_single_row_bug():
             continue
         tol = ar.NORM_TOL_FWD if name == "out" else ar.NORM_TOL_BWD
         assert ar.rel_err(x, r) < tol, name
-    rep, bad = ar.check_case(got, q, k, v, True, do, ref=ref)
+    rep, bad = ar.check_plain(got, q, k, v, True, do, ref=ref)
     assert any(b.startswith("lse: max err") for b in bad), bad
 
 

@@ -11,7 +11,6 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import attn_ref as ar  # noqa: E402
-import attn_window_ref as wr  # noqa: E402
 
 
 # ---------------------------------------------------------------------------
@@ -19,17 +18,22 @@ import attn_window_ref as wr  # noqa: E402
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("hkv", [3, 1])
 def test_zero_bound_is_the_causal_reference(hkv):
-    q, k, v, do = ar.make_inputs("randn", 2, 3, hkv, 192, 64)
-    for lo in (torch.zeros(192, dtype=torch.int32),
-               torch.zeros(2, 192, dtype=torch.int32)):
-        for a, b in zip(wr.ref64_lo(q, k, v, lo, do),
-                        ar.ref64(q, k, v, True, do)):
-            assert torch.equal(a, b)
-        for a, b in zip(wr.base_bf16_lo(q, k, v, lo, do),
-                        ar.base_bf16(q, k, v, True, do)):
-            assert torch.equal(a, b)
-        assert wr.lse_tolerance_lo(q, k, lo, ar.ref64(q, k, v, True)[1]) == \
-            ar.lse_tolerance(q, k, True, ar.ref64(q, k, v, True)[1])
+    """lo=None skips the bound's operations, a zero bound runs them: neutral
+    arguments must not change a bit of the truth, the floor or the LSE
+    tolerance."""
+    T = 192
+    q, k, v, do = ar.make_inputs("randn", 2, 3, hkv, T, 64)
+    ref, base = ar.ref64(q, k, v, True, do), ar.base_bf16(q, k, v, True, do)
+    assert len(ref) == len(base) == 5
+    for lo in (torch.zeros(T, dtype=torch.int32),
+               torch.zeros(2, T, dtype=torch.int32)):
+        for name, a, b in zip(ar.NAMES, ar.ref64(q, k, v, True, do, lo=lo), ref):
+            assert a.dtype == b.dtype and torch.equal(a, b), name
+        for name, a, b in zip(ar.NAMES,
+                              ar.base_bf16(q, k, v, True, do, lo=lo), base):
+            assert a.dtype == b.dtype and torch.equal(a, b), name
+        assert ar.lse_tolerance(q, k, ar.allowed(T, True, lo=lo), ref[1]) == \
+            ar.lse_tolerance(q, k, ar.allowed(T, True), ref[1])
 
 
 # ---------------------------------------------------------------------------
@@ -47,22 +51,22 @@ MUTANTS = {
 }
 
 
-@pytest.mark.parametrize("D,bound,kind", wr.MATRIX,
-                         ids=[f"D{d}-{b}-{k}" for d, b, k in wr.MATRIX])
+@pytest.mark.parametrize("D,bound,kind", ar.MATRIX_WINDOW,
+                         ids=[f"D{d}-{b}-{k}" for d, b, k in ar.MATRIX_WINDOW])
 def test_criterion_rejects_planted_bugs(D, bound, kind):
-    T = wr.BOUNDS[bound][0]
-    c = wr.case(kind, *wr.BH, wr.BH[1], T, D, bound)
+    T = ar.BOUNDS[bound][0]
+    c = ar.case(kind, *ar.BH_WINDOW, ar.BH_WINDOW[1], T, D, bound=bound)
     q, k, v, do, lo = (c[n] for n in ("q", "k", "v", "do", "lo"))
     # the clean floor passes its own criterion
-    _, bad = wr.check_case_lo(c["base"], c["ref"], c["base"], c["lse_tol"])
+    _, bad = ar.check_case(c["base"], c["ref"], c["base"], c["lse_tol"])
     assert not bad, bad
     for name, (must, noop) in MUTANTS.items():
-        got = wr.base_bf16_lo(q, k, v, lo, do, mut=(name,))
+        got = ar.base_bf16(q, k, v, True, do, lo=lo, mut=(name,))
         if bound in noop:
             assert all(torch.equal(a, b) for a, b in zip(got, c["base"]))
             continue
-        _, bad = wr.check_case_lo(got, c["ref"], c["base"], c["lse_tol"])
-        missed = must - wr.rejected(bad)
+        _, bad = ar.check_case(got, c["ref"], c["base"], c["lse_tol"])
+        missed = must - ar.rejected(bad)
         assert not missed, (name, sorted(missed), bad)
 
 
@@ -83,7 +87,7 @@ def test_window_lo_matches_loop(T, W):
 
     lo = window_lo(T, W, "cpu")
     assert lo.dtype == torch.int32 and lo.shape == (T,)
-    assert torch.equal(lo, wr.window_bound(T, W))
+    assert torch.equal(lo, ar.window_bound(T, W))
     assert _monotone_le_t(lo)
     assert window_lo(T, W, "cpu") is lo          # cached
     with pytest.raises(ValueError):
@@ -165,11 +169,11 @@ def test_window_and_documents_combine_to_the_maximum():
 def test_attention_math_with_bound_matches_fp64(bound):
     from saturn_amd.ops.functional import attention_math, causal_attention
 
-    T = wr.BOUNDS[bound][0]
+    T = ar.BOUNDS[bound][0]
     g = torch.Generator().manual_seed(11)
     q, k, v = (torch.randn(2, 3, T, 64, generator=g) for _ in range(3))
-    lo = wr.make_bound(bound)
-    ref, _ = wr.ref64_lo(q, k, v, lo)           # fp32 inputs, upcast exactly
+    lo = ar.make_bound(bound)
+    ref, _ = ar.ref64(q, k, v, True, lo=lo)         # fp32 inputs, upcast exactly
     out = attention_math(q, k, v, kv_lo=lo)
     assert out.dtype == torch.float32
     assert (out.double() - ref).abs().max().item() < 1e-6

@@ -1,7 +1,7 @@
 """Attention with a per-row lower key bound (kv_lo: sliding windows, packed
 documents) on the GPU: attention.hip's LO instantiations through ext.attn_fwd
 / ext.attn_bwd and saturn_amd.ops.flash, against the fp64 reference of
-tests/attn_window_ref.py under attn_ref's `close` criterion, plus the exact
+tests/attn_ref.py under its `close` criterion, plus the exact
 bitwise properties a correct mask and a correct tile skip must have.
 
 Every shape has B*H <= 16 and T <= 384.  Each comparison prints an
@@ -12,7 +12,6 @@ floor, per tensor); docs/kernels.md tabulates the worst per group.
 import json
 import math
 import os
-import subprocess
 import sys
 
 import pytest
@@ -20,17 +19,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import attn_ref as ar  # noqa: E402
-import attn_window_ref as wr  # noqa: E402
+import attn_run as run  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-DS = list(wr.DS)
-
-
-def _ext():
-    from saturn_amd.ops import require_ext
-
-    return require_ext()
+DS = list(ar.DS)
 
 
 def _lo_paths(T, D):
@@ -44,17 +37,12 @@ def _lo_paths(T, D):
 def _check(group, name, c, gqa=False):
     """Both routes for a case; they must agree bit for bit (dk/dv under GQA
     excepted: fp32 atomics in arrival order); the direct five are checked."""
-    direct, public = wr.run_case(c, DEV)
-    assert wr.bits_equal(public[0], direct[0]), "out: routes differ"
-    assert wr.bits_equal(public[1], direct[2]), "dq: routes differ"
-    if not gqa:
-        assert wr.bits_equal(public[2], direct[3]), "dk: routes differ"
-        assert wr.bits_equal(public[3], direct[4]), "dv: routes differ"
+    direct, public = run.both_routes(c, gqa)
     routes = [direct]
     if gqa:
         routes.append((public[0], direct[1]) + public[1:])
     for got in routes:
-        rep, bad = wr.check_case_lo(got, c["ref"], c["base"], c["lse_tol"])
+        rep, bad = ar.check_case(got, c["ref"], c["base"], c["lse_tol"])
         print("ATTN_RATIO", f"window-{group}", name, json.dumps(ar.ratios(rep)),
               "lse", json.dumps(rep.get("lse")))
         assert not bad, bad
@@ -65,22 +53,26 @@ def _dev(c):
     return tuple(c[n].to(DEV) for n in ("q", "k", "v", "do", "lo"))
 
 
+def _direct(q, k, v, do, lo):
+    return run.kernel_direct(q, k, v, True, do, lo=lo)
+
+
 # ---------------------------------------------------------------------------
 # A. the matrix: D x bound x input kind
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("D,bound,kind", wr.MATRIX,
-                         ids=[f"D{d}-{b}-{k}" for d, b, k in wr.MATRIX])
+@pytest.mark.parametrize("D,bound,kind", ar.MATRIX_WINDOW,
+                         ids=[f"D{d}-{b}-{k}" for d, b, k in ar.MATRIX_WINDOW])
 def test_matrix(D, bound, kind):
-    T = wr.BOUNDS[bound][0]
-    path = _ext().attn_dispatch(T, D, has_lo=True)
+    T = ar.BOUNDS[bound][0]
+    path = run.ext().attn_dispatch(T, D, has_lo=True)
     assert path == _lo_paths(T, D)
     # T=192 and T=320 reach v1; T=256 and T=384 reach v2 at D <= 128
     v2 = T in (256, 384) and D <= 128
     assert path.startswith(f"attn_fwd_v2_kernel<{D},1>" if v2
                            else f"attn_fwd_kernel<{D},1>")
     # without the keyword the report is the plain one
-    assert ",1>" not in _ext().attn_dispatch(T, D).split()[0]
-    c = wr.case(kind, *wr.BH, wr.BH[1], T, D, bound)
+    assert ",1>" not in run.ext().attn_dispatch(T, D).split()[0]
+    c = ar.case(kind, *ar.BH_WINDOW, ar.BH_WINDOW[1], T, D, bound=bound)
     _check("A", f"D{D}-{bound}-{kind}", c)
 
 
@@ -91,17 +83,17 @@ def test_matrix(D, bound, kind):
 @pytest.mark.parametrize("D", DS)
 def test_zero_bound_is_the_plain_kernel(D, T):
     q, k, v, do = ar.make_inputs("randn", 2, 3, 3, T, D, DEV, seed=1)
-    plain = ar.ext_fwd_bwd(q, k, v, True, do, T)
+    plain = run.ext_fwd_bwd(q, k, v, True, do, T)
     for lo in (torch.zeros(T, dtype=torch.int32, device=DEV),
                torch.zeros(2, T, dtype=torch.int32, device=DEV)):
-        got = wr.kernel_direct_lo(q, k, v, do, lo)
+        got = _direct(q, k, v, do, lo)
         for name, a, b in zip(ar.NAMES, got, plain):
-            assert wr.bits_equal(a, b), name
-    ref = ar.kernel_public(q, k, v, True, do)
+            assert run.bits_equal(a, b), name
+    ref = run.kernel_public(q, k, v, True, do)
     for W in (T, T + 5):
-        got = wr.kernel_public_lo(q, k, v, do, window=W)
+        got = run.kernel_public(q, k, v, True, do, window=W)
         for a, b in zip(got, ref):
-            assert wr.bits_equal(a, b), W
+            assert run.bits_equal(a, b), W
 
 
 # ---------------------------------------------------------------------------
@@ -116,26 +108,26 @@ def _other(t, seed):
 def test_window_locality_bitwise(D):
     T, W, j0, t0 = 256, 40, 100, 150
     q, k, v, do = ar.make_inputs("randn", 1, 3, 3, T, D, DEV, seed=3)
-    lo = wr.window_bound(T, W).to(DEV)
-    a = wr.kernel_direct_lo(q, k, v, do, lo)
+    lo = ar.window_bound(T, W).to(DEV)
+    a = _direct(q, k, v, do, lo)
     # keys below j0 replaced: rows t >= j0 + W - 1 never saw them
     k2, v2 = k.clone(), v.clone()
     k2[:, :, :j0] = _other(k[:, :, :j0], 1)
     v2[:, :, :j0] = _other(v[:, :, :j0], 2)
-    b = wr.kernel_direct_lo(q, k2, v2, do, lo)
+    b = _direct(q, k2, v2, do, lo)
     r0 = j0 + W - 1
     for i in (0, 1, 2):                                   # out, lse, dq
-        assert wr.bits_equal(a[i][:, :, r0:], b[i][:, :, r0:]), ar.NAMES[i]
-        assert not wr.bits_equal(a[i][:, :, :r0], b[i][:, :, :r0])
+        assert run.bits_equal(a[i][:, :, r0:], b[i][:, :, r0:]), ar.NAMES[i]
+        assert not run.bits_equal(a[i][:, :, :r0], b[i][:, :, :r0])
     # rows from t0 replaced: keys j <= t0 - W are seen by earlier rows only
     q2, do2 = q.clone(), do.clone()
     q2[:, :, t0:] = _other(q[:, :, t0:], 3)
     do2[:, :, t0:] = _other(do[:, :, t0:], 4)
-    b = wr.kernel_direct_lo(q2, k, v, do2, lo)
+    b = _direct(q2, k, v, do2, lo)
     j1 = t0 - W + 1
     for i in (3, 4):                                      # dk, dv
-        assert wr.bits_equal(a[i][:, :, :j1], b[i][:, :, :j1]), ar.NAMES[i]
-        assert not wr.bits_equal(a[i][:, :, j1:], b[i][:, :, j1:])
+        assert run.bits_equal(a[i][:, :, :j1], b[i][:, :, :j1]), ar.NAMES[i]
+        assert not run.bits_equal(a[i][:, :, j1:], b[i][:, :, j1:])
 
 
 @pytest.mark.parametrize("D", DS)
@@ -143,20 +135,20 @@ def test_document_locality_bitwise(D):
     T, docs = 256, [70, 1, 129, 56]
     s3, e3 = 71, 200                                      # document 3
     q, k, v, do = ar.make_inputs("randn", 1, 3, 3, T, D, DEV, seed=4)
-    lo = wr.docs_bound([docs], T).to(DEV)
-    a = wr.kernel_direct_lo(q, k, v, do, lo)
+    lo = ar.docs_bound([docs], T).to(DEV)
+    a = _direct(q, k, v, do, lo)
     inside = [t.clone() for t in (q, k, v, do)]
     for i, t in enumerate(inside):
         t[:, :, s3:e3] = _other(t[:, :, s3:e3], 10 + i)
-    b = wr.kernel_direct_lo(*inside, lo)
+    b = _direct(*inside, lo)
     for i, name in enumerate(ar.NAMES):
-        assert wr.bits_equal(a[i][:, :, :s3], b[i][:, :, :s3]), name
-        assert wr.bits_equal(a[i][:, :, e3:], b[i][:, :, e3:]), name
-        assert not wr.bits_equal(a[i][:, :, s3:e3], b[i][:, :, s3:e3])
+        assert run.bits_equal(a[i][:, :, :s3], b[i][:, :, :s3]), name
+        assert run.bits_equal(a[i][:, :, e3:], b[i][:, :, e3:]), name
+        assert not run.bits_equal(a[i][:, :, s3:e3], b[i][:, :, s3:e3])
     # no other document contributes to document 3's dk / dv
     do0 = do.clone()
     do0[:, :, s3:e3] = 0
-    z = wr.kernel_direct_lo(q, k, v, do0, lo)
+    z = _direct(q, k, v, do0, lo)
     assert (z[3][:, :, s3:e3].float() == 0).all()
     assert (z[4][:, :, s3:e3].float() == 0).all()
     assert (z[3][:, :, e3:].float() != 0).any()
@@ -168,10 +160,10 @@ def test_document_locality_bitwise(D):
 @pytest.mark.parametrize("T", [192, 256])
 @pytest.mark.parametrize("D", DS)
 def test_window_of_one(D, T):
-    c = wr.case("randn", 1, 3, 3, T, D, ("window", 1), seed=5)
+    c = ar.case("randn", 1, 3, 3, T, D, bound=("window", 1), seed=5)
     q, k, v, do, lo = _dev(c)
-    out, lse, dq, dk, dv = wr.kernel_direct_lo(q, k, v, do, lo)
-    assert wr.bits_equal(out, v) and wr.bits_equal(dv, do)   # p = 1 exactly
+    out, lse, dq, dk, dv = _direct(q, k, v, do, lo)
+    assert run.bits_equal(out, v) and run.bits_equal(dv, do)   # p = 1 exactly
     diag = (q.double() * k.double()).sum(-1) / math.sqrt(D)   # the one score
     assert ar.max_err(c["ref"][1], diag.cpu()) < 1e-12
     err = ar.max_err(lse, diag)
@@ -195,10 +187,10 @@ def test_window_of_one(D, T):
 @pytest.mark.parametrize("D", [128, 256])
 def test_window_tile_edges(D, W):
     T = 256
-    path = _ext().attn_dispatch(T, D, has_lo=True)
+    path = run.ext().attn_dispatch(T, D, has_lo=True)
     assert path.startswith("attn_fwd_v2_kernel<128,1>" if D == 128
                            else "attn_fwd_kernel<256,1>")
-    c = wr.case("randn", 1, 3, 3, T, D, ("window", W), seed=6)
+    c = ar.case("randn", 1, 3, 3, T, D, bound=("window", W), seed=6)
     _check("E", f"D{D}W{W}", c)
 
 
@@ -213,23 +205,22 @@ def test_window_tile_edges(D, W):
 def test_ragged_T(D, T, bound):
     from saturn_amd.ops.flash import document_lo
 
-    c = wr.case("randn", 2, 3, 3, T, D, bound, seed=7)
+    c = ar.case("randn", 2, 3, 3, T, D, bound=bound, seed=7)
     q, k, v, do, lo = _dev(c)
     if bound[0] == "window":
-        got = wr.kernel_public_lo(q, k, v, do, window=bound[1])
+        got = run.kernel_public(q, k, v, True, do, window=bound[1])
     else:
         ids = torch.ones(2, T, dtype=torch.long, device=DEV)
         ids[:, 99] = 0                                    # ends document 1
         assert torch.equal(document_lo(ids, 0), lo)
-        got = wr.kernel_public_lo(q, k, v, do, kv_lo=document_lo(ids, 0))
+        got = run.kernel_public(q, k, v, True, do, lo=document_lo(ids, 0))
     for t in got:
         assert torch.isfinite(t.float()).all()
     # LSE comes from the direct route, padded as the wrapper pads
-    direct = wr.kernel_direct_lo(q, k, v, do, lo)
+    direct = _direct(q, k, v, do, lo)
     for i, j in ((0, 0), (1, 2), (2, 3), (3, 4)):
-        assert wr.bits_equal(got[i], direct[j]), ar.NAMES[j]
-    rep, bad = wr.check_case_lo(tuple(t.cpu() for t in direct), c["ref"],
-                                c["base"], c["lse_tol"])
+        assert run.bits_equal(got[i], direct[j]), ar.NAMES[j]
+    rep, bad = ar.check_case(direct, c["ref"], c["base"], c["lse_tol"])
     print("ATTN_RATIO window-F", f"D{D}T{T}{bound[0]}", json.dumps(ar.ratios(rep)),
           "lse", json.dumps(rep.get("lse")))
     assert not bad, bad
@@ -241,7 +232,7 @@ def test_ragged_T(D, T, bound):
 @pytest.mark.parametrize("H,Hkv", [(8, 2), (4, 1)])
 @pytest.mark.parametrize("D", DS)
 def test_gqa(D, H, Hkv):
-    c = wr.case("randn", 1, H, Hkv, 192, D, ("window", 33), seed=8)
+    c = ar.case("randn", 1, H, Hkv, 192, D, bound=("window", 33), seed=8)
     _check("G", f"D{D}H{H}kv{Hkv}", c, gqa=True)
 
 
@@ -250,12 +241,12 @@ def test_gqa(D, H, Hkv):
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("D", DS)
 def test_run_to_run_bitwise(D):
-    c = wr.case("randn", *wr.BH, wr.BH[1], 256, D, "docs_T256")
+    c = ar.case("randn", *ar.BH_WINDOW, ar.BH_WINDOW[1], 256, D, bound="docs_T256")
     args = _dev(c)
-    a = wr.kernel_direct_lo(*args)
-    b = wr.kernel_direct_lo(*args)
+    a = _direct(*args)
+    b = _direct(*args)
     for name, x, y in zip(ar.NAMES, a, b):
-        assert wr.bits_equal(x, y), name
+        assert run.bits_equal(x, y), name
 
 
 # ---------------------------------------------------------------------------
@@ -264,7 +255,7 @@ def test_run_to_run_bitwise(D):
 def test_refusals():
     from saturn_amd.ops.flash import flash_attention
 
-    ext = _ext()
+    ext = run.ext()
     B, H, T, D = 2, 2, 128, 64
     q, k, v, do = ar.make_inputs("randn", B, H, H, T, D, DEV, seed=9)
     lo = torch.zeros(B, T, dtype=torch.int32, device=DEV)
@@ -294,67 +285,29 @@ def test_refusals():
     with pytest.raises(RuntimeError, match="causal"):
         ext.attn_bwd(do, q, k, v, o, lse, False, T, kv_lo=lo)
     # a [T] bound is the [B, T] bound with batch stride 0
-    lo1 = wr.window_bound(T, 9).to(DEV)
-    a = wr.kernel_direct_lo(q, k, v, do, lo1)
-    b = wr.kernel_direct_lo(q, k, v, do, lo1.expand(B, T).contiguous())
+    lo1 = ar.window_bound(T, 9).to(DEV)
+    a = _direct(q, k, v, do, lo1)
+    b = _direct(q, k, v, do, lo1.expand(B, T).contiguous())
     for name, x, y in zip(ar.NAMES, a, b):
-        assert wr.bits_equal(x, y), name
-
-
-# child time limit, by the rule of the switch children of
-# test_attention_gpu.py: START_UP_S + FACTOR x the same work measured in
-# this process (interpreter + torch import + device start-up and code-object
-# load on a shared machine, then the work with 10x headroom)
-START_UP_S = 120.0
-FACTOR = 10.0
-SWITCHES = ("SAMD_ATTN_V2", "SAMD_ATTN_BWD_TR16", "SAMD_ATTN_BWD_VL2",
-            "SAMD_ATTN_DQ_GKV")
-_state = {"seconds": None, "child_died": False}
+        assert run.bits_equal(x, y), name
 
 
 def _own_seconds():
-    if _state["seconds"] is None:
-        wr.child_matrix(DEV)                          # warm
-        res = wr.child_matrix(DEV)
-        assert not res["failures"], res["failures"]
-        assert res["path"] == _lo_paths(256, 128)
-        _state["seconds"] = res["seconds"]
-    return _state["seconds"]
-
-
-def _child(mode, setting):
-    if _state["child_died"]:
-        pytest.skip("an earlier child ended by signal, abort or timeout: no "
-                    "further child is started")
-    if ar.device_error:
-        pytest.fail("not started: device error earlier in this process: "
-                    + ar.device_error[0])
-    limit = START_UP_S + FACTOR * _own_seconds()
-    env = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-    env.update(setting)
-    cmd = [sys.executable, os.path.abspath(wr.__file__), "--child", mode]
-    try:
-        p = subprocess.run(cmd, env=env, timeout=limit, capture_output=True,
-                           text=True)
-    except subprocess.TimeoutExpired:
-        _state["child_died"] = True
-        pytest.fail(f"{setting}: child exceeded its {limit:.0f} s limit")
-    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
-    if (p.returncode != 0 or not lines or "HIP error" in p.stderr
-            or "hipError" in p.stderr):
-        _state["child_died"] = True
-        pytest.fail(f"{setting}: child status {p.returncode}\n{p.stderr[-2000:]}")
-    return json.loads(lines[-1])
+    res = run.own_run("window-matrix")
+    assert res["path"] == _lo_paths(256, 128)
+    return res["seconds"]
 
 
 def test_child_vl2_is_refused_by_name():
-    res = _child("refuse", {"SAMD_ATTN_BWD_VL2": "1"})
+    res, _, _ = run.run_child("window-refuse", {"SAMD_ATTN_BWD_VL2": "1"},
+                               _own_seconds())
     assert res["refused"], res
     assert "SAMD_ATTN_BWD_VL2" in res["message"], res
 
 
 def test_child_v2_off_takes_v1():
-    res = _child("matrix", {"SAMD_ATTN_V2": "0"})
+    res, _, _ = run.run_child("window-matrix", {"SAMD_ATTN_V2": "0"},
+                               _own_seconds())
     print("ATTN_WINDOW_CHILD SAMD_ATTN_V2=0", json.dumps(res))
     assert res["path"].startswith("attn_fwd_kernel<128,1>"), res["path"]
     assert not res["failures"], res["failures"]
@@ -385,10 +338,10 @@ def test_model_window_locality_bitwise():
     torch.cuda.synchronize()
     # every op but attention is row-wise; two layers of W-1 keys of reach
     far = 2 * (W - 1) + 1
-    assert wr.bits_equal(a[:, far:], b[:, far:])
-    assert not wr.bits_equal(a[:, :far], b[:, :far])
+    assert run.bits_equal(a[:, far:], b[:, far:])
+    assert not run.bits_equal(a[:, :far], b[:, :far])
     with torch.no_grad():
-        assert not wr.bits_equal(_llama(None)(x)[:, far:], a[:, far:])
+        assert not run.bits_equal(_llama(None)(x)[:, far:], a[:, far:])
 
 
 def test_model_window_covering_T_is_the_plain_model():
@@ -404,6 +357,6 @@ def test_model_window_covering_T_is_the_plain_model():
         llama_loss(logits, x).backward()
         torch.cuda.synchronize()
         res.append((logits.detach(), {n: p.grad for n, p in m.named_parameters()}))
-    assert wr.bits_equal(res[0][0], res[1][0])
+    assert run.bits_equal(res[0][0], res[1][0])
     for n, g in res[0][1].items():
-        assert g is not None and wr.bits_equal(g, res[1][1][n]), n
+        assert g is not None and run.bits_equal(g, res[1][1][n]), n
