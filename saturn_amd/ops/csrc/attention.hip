@@ -5,7 +5,7 @@
 // fp32 [T,T] score tensor) with one MFMA kernel using online softmax
 // (O(T) memory) and fp32 accumulation.
 //
-// Five kernels, all 256 threads = 4 waves, bh on grid.x (fastest) and the
+// Six kernels, all 256 threads = 4 waves, bh on grid.x (fastest) and the
 // tile index on grid.y, K/V/Q/dO tiles staged in dynamic LDS:
 //   attn_fwd_kernel     v1 forward, 64 q rows per block (16 per wave), kv
 //                       tiles of 32 keys: S[16][32] on 16x16x32 MFMAs,
@@ -20,6 +20,9 @@
 //                       accumulates dK/dV in registers.
 //   attn_dq_kernel      dQ: one block per 64 q rows loops over key tiles of
 //                       32 and accumulates dQ in registers (no atomics).
+//   attn_dq_ds_kernel   dQ at D = 256 from the bf16 dS that attn_bwd_kernel
+//                       <..., DSOUT> stored: one GEMM unit instead of three,
+//                       the same bits (route chosen by use_ds_route).
 // The host part at the end of the file picks the instantiations: attn_plan
 // turns (T, D, kv_lo?) and the environment switches into a plan, one
 // selection routine per kernel family maps the plan to a variant (typed
@@ -702,7 +705,9 @@ __global__ void attn_delta_kernel(const unsigned short* __restrict__ dO,
   }
 }
 
-template <int D, bool TR16, bool VL2, bool LO, bool DROP>
+// DSOUT: also store the bf16 dS values (the ones written to lds.dst) into the
+// global scratch DS[bh][q][key], row length T, for attn_dq_ds_kernel.
+template <int D, bool TR16, bool VL2, bool LO, bool DROP, bool DSOUT = false>
 __launch_bounds__(256, 2)
 __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
                                 const unsigned short* __restrict__ Q,
@@ -720,7 +725,8 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
                                 TStr dks, TStr dvs,
                                 const int* __restrict__ KVLO, long lo_sb,
                                 unsigned long long seed, unsigned thr,
-                                float drop_r) {
+                                float drop_r,
+                                unsigned short* __restrict__ DS) {
   using namespace bwd;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool HASV = (D <= 128) && !VL2;  // V tile LDS-resident?
@@ -829,6 +835,7 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
       if constexpr (DROP)
         zdraw = attn_rng_draw(attn_rng_row(seed, bh, q0 + n * 16 + r),
                               kv0 + wid * 16 + qg * 4);
+      unsigned short dsk[4];  // DSOUT: this lane's four dS values
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
         const int key_loc = qg * 4 + reg;           // within wave's 16 keys
@@ -852,7 +859,18 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
           const float dsv = p * (dpt[reg] - lds.delta_t[n * 16 + r]) * scale;
           lds.pt[wid][key_loc][n * 16 + r] = f2us(p);
           lds.dst[wid * 16 + key_loc][n * 16 + r] = f2us(dsv);
+          if constexpr (DSOUT) dsk[reg] = f2us(dsv);
         }
+      }
+      // keys kv0 + wid*16 + qg*4 + 0..3 of q row q0 + n*16 + r: one 8-byte
+      // store (T % 64 == 0 and a 16-B aligned base keep it aligned)
+      if constexpr (DSOUT) {
+        uint2 w;
+        w.x = (unsigned)dsk[0] | ((unsigned)dsk[1] << 16);
+        w.y = (unsigned)dsk[2] | ((unsigned)dsk[3] << 16);
+        *reinterpret_cast<uint2*>(
+            DS + (bh * T + q0 + n * 16 + r) * (long)T + kv0 + wid * 16 +
+            qg * 4) = w;
       }
     }
 
@@ -1166,6 +1184,151 @@ __global__ void attn_dq_kernel(const unsigned short* __restrict__ dO,
   }
 }
 
+// ---------------------------------------------------------------------------
+// dQ from stored dS.  attn_bwd_kernel<..., DSOUT> leaves the bf16 dS it
+// computes anyway in a global scratch dS[bh][q][key]; this kernel reads it
+// back as the A fragment of the one GEMM unit dQ needs (dQ = dS K) instead of
+// recomputing S^T and dP^T (two more units, Q/dO/V/LSE/delta, exp, shuffles).
+//
+// Same bits as attn_dq_kernel<D,0,0,0,0>: both kernels compute dS with one
+// instruction sequence (same MFMA operands and chunk order, same expression,
+// same rounding), and this kernel keeps the accumulation: per acc[dt] one
+// 16x16x32 MFMA per 32 keys, key tiles ascending from 0, A slot j of lane
+// group qg = key k0 + qg*8 + j, B = K rows qg*8 + j, and the same causal
+// skip of a wave's fully masked 32-key tiles.
+//
+// Every dS element read here was written: the dK/dV block of keys
+// [kb*64, kb*64+64) stores all q rows >= (causal ? kb*64 : 0) up to T, for
+// every key of its block whatever kv_len is (masked entries store p = 0
+// products); this block reads keys < (causal ? q0+64 : T) of rows >= q0,
+// i.e. key blocks kb <= q0/64 when causal.
+//
+// 64 keys per staging step: 33.8 KB of LDS and <= 128 VGPRs, four blocks per
+// CU hide each other's staging.  The transposed B fragments come through the
+// ds_read_tr16_b64 builtin (the instruction of tr16_bfrag, scheduled by the
+// compiler with counted waits).
+// ---------------------------------------------------------------------------
+namespace dqds {
+constexpr int QB = 64;  // q rows per block (4 waves x 16)
+constexpr int KT = 64;  // keys per staging step (two MFMA tiles of 32)
+}  // namespace dqds
+
+template <int D>
+struct AttnDqDsLds {
+  unsigned short kt[dqds::KT][D + 8];
+};
+
+// B[(l>>4)*8 + j][l&15] of the row-major LDS tile at tile_row0 (see the
+// tr16_bfrag comment for the lane -> address map)
+template <int ROWPITCH>
+__device__ __forceinline__ bf16x8 tr16_bfrag_b(const unsigned short* tile_row0,
+                                               int lane) {
+  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+  const unsigned short* p =
+      tile_row0 + ((lane >> 2) & 3) * ROWPITCH + 4 * (lane & 3);
+  bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)p);
+  bf16x4 v1 =
+      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(p + 4 * ROWPITCH));
+  return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+template <int D>
+__launch_bounds__(256, 4)
+__global__ void attn_dq_ds_kernel(const unsigned short* __restrict__ DS,
+                                  const unsigned short* __restrict__ K,
+                                  unsigned short* __restrict__ dQ16, int T,
+                                  int n_heads, int causal, TStr ks, TStr dqs) {
+  using namespace dqds;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  AttnDqDsLds<D>& lds = *reinterpret_cast<AttnDqDsLds<D>*>(smem);
+
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int r = lane & 15;
+  const int qg = lane >> 4;
+  // causal: the q blocks with the most key tiles start first
+  const int q0 = (gridDim.y - 1 - blockIdx.y) * QB;
+  const long bh = blockIdx.x;
+  const long b = bh / n_heads, h = bh % n_heads;
+  const unsigned short* Kh = K + b * ks.sb + h * ks.sh;  // Hkv == H here
+  // this lane's A-fragment run: dS[q0 + wid*16 + r][k0 + qg*8 .. +7]
+  const unsigned short* ds_row =
+      DS + (bh * T + q0 + wid * 16 + r) * (long)T + qg * 8;
+
+  f32x4 acc[D / 16];
+#pragma unroll
+  for (int dt = 0; dt < D / 16; ++dt) acc[dt] = {0.f, 0.f, 0.f, 0.f};
+
+  const int k_end = causal ? (q0 + QB < T ? q0 + QB : T) : T;
+  for (int k0 = 0; k0 < k_end; k0 += KT) {
+    // The skip rule of attn_dq_kernel at its 32-key granularity: a wave whose
+    // 16 q rows are all left of a 32-key tile leaves it out.  k0 <= q0 when
+    // causal, so the first tile of a step is always live.
+    const bool live1 = !(causal && k0 + 32 > q0 + wid * 16 + 15);
+    const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(ds_row + k0);
+    bf16x8 a1 = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (live1) a1 = *reinterpret_cast<const bf16x8*>(ds_row + k0 + 32);
+
+    // stage the K tile in two halves: a batch of loads in flight at a time
+    // and few enough VGPRs for four waves per SIMD without spilling
+    constexpr int CHUNKS = (KT * D) / (256 * 8);
+    constexpr int HALF = CHUNKS / 2;
+    __syncthreads();  // previous step's tile fully consumed
+#pragma unroll
+    for (int hb = 0; hb < CHUNKS; hb += HALF) {
+      bf16x8 kreg[HALF];
+#pragma unroll
+      for (int c = 0; c < HALF; ++c) {
+        int idx = ((hb + c) * 256 + threadIdx.x) * 8;
+        int row = idx / D, col = idx % D;
+        kreg[c] = *reinterpret_cast<const bf16x8*>(
+            Kh + (long)(k0 + row) * ks.st + col);
+      }
+#pragma unroll
+      for (int c = 0; c < HALF; ++c) {
+        int idx = ((hb + c) * 256 + threadIdx.x) * 8;
+        int row = idx / D, col = idx % D;
+        *reinterpret_cast<bf16x8*>(&lds.kt[row][col]) = kreg[c];
+      }
+    }
+    __syncthreads();
+
+    // ---- dQ += dS @ K, keys k0..k0+31 then k0+32..k0+63 per accumulator
+    if (live1) {
+#pragma unroll
+      for (int dt = 0; dt < D / 16; dt += 2) {
+        bf16x8 b00 = tr16_bfrag_b<D + 8>(&lds.kt[qg * 8][dt * 16], lane);
+        bf16x8 b01 = tr16_bfrag_b<D + 8>(&lds.kt[qg * 8][dt * 16 + 16], lane);
+        bf16x8 b10 = tr16_bfrag_b<D + 8>(&lds.kt[32 + qg * 8][dt * 16], lane);
+        bf16x8 b11 =
+            tr16_bfrag_b<D + 8>(&lds.kt[32 + qg * 8][dt * 16 + 16], lane);
+        acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b00, acc[dt], 0, 0, 0);
+        acc[dt + 1] =
+            __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b01, acc[dt + 1], 0, 0, 0);
+        acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b10, acc[dt], 0, 0, 0);
+        acc[dt + 1] =
+            __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b11, acc[dt + 1], 0, 0, 0);
+      }
+    } else {
+#pragma unroll
+      for (int dt = 0; dt < D / 16; ++dt) {
+        bf16x8 b0 = tr16_bfrag_b<D + 8>(&lds.kt[qg * 8][dt * 16], lane);
+        acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[dt], 0, 0, 0);
+      }
+    }
+  }
+
+  // ---- store dQ once, bf16, [B,T,H,D]-physical strides
+  unsigned short* dQh = dQ16 + b * dqs.sb + h * dqs.sh;
+#pragma unroll
+  for (int reg = 0; reg < 4; ++reg) {
+    const int q_glob = q0 + wid * 16 + qg * 4 + reg;
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt)
+      dQh[(long)q_glob * dqs.st + dt * 16 + r] = f2us(acc[dt][reg]);
+  }
+}
+
 // ===========================================================================
 // Host part: plan -> variant -> launch.
 // ===========================================================================
@@ -1242,6 +1405,54 @@ static AttnPlan attn_plan(int T, int D, bool has_lo, bool bwd = true,
                   has_drop};
 }
 
+// dQ from stored dS (attn_bwd_kernel<..., DSOUT> + attn_dq_ds_kernel) instead
+// of recomputing S^T / dP^T in attn_dq_kernel.  Default ON where eligible;
+// SAMD_ATTN_DQ_DS=0 keeps the recompute route for the whole process.
+static bool sw_dq_ds() {
+  static const bool v = !env_is("SAMD_ATTN_DQ_DS", '0');
+  return v;
+}
+// Largest dS scratch (B*H*T*T bf16) the stored-dS route takes: the flagship
+// call's own size (B16 H16 T512), half of the 256 MB Infinity Cache, and the
+// largest size the route has been measured at.  Larger calls keep the
+// recompute route.
+constexpr int64_t DS_SCRATCH_MAX_BYTES = int64_t(128) << 20;
+
+// The one place that decides the dQ route.  nullptr: the call is eligible
+// for the stored-dS route; otherwise the reason it is not.
+static const char* ds_route_refusal(int64_t B, int64_t H, int64_t Hkv,
+                                    int64_t T, int64_t D, bool has_lo,
+                                    bool has_drop) {
+  if (D != 256) return "the stored-dS dQ route is built for D == 256 only";
+  if (has_lo) return "the stored-dS dQ route is not built for kv_lo";
+  if (has_drop) return "the stored-dS dQ route is not built for dropout_p > 0";
+  if (Hkv != H) return "the stored-dS dQ route needs Hkv == H (no GQA)";
+  if (sw_dq_gkv())
+    return "the stored-dS dQ route is not taken with SAMD_ATTN_DQ_GKV=1";
+  if (B * H * T * T * 2 > DS_SCRATCH_MAX_BYTES)
+    return "the dS scratch (B*H*T*T bf16) exceeds the 128 MiB bound of the "
+           "stored-dS dQ route";
+  return nullptr;
+}
+bool attn_ds_eligible(int64_t B, int64_t H, int64_t Hkv, int64_t T, int64_t D,
+                      bool has_lo, bool has_drop) {
+  return ds_route_refusal(B, H, Hkv, T, D, has_lo, has_drop) == nullptr;
+}
+// dq_route: -1 auto, 0 recompute, 1 stored dS (an error if not eligible).
+static bool use_ds_route(int64_t dq_route, int64_t B, int64_t H, int64_t Hkv,
+                         int64_t T, int64_t D, bool has_lo, bool has_drop,
+                         const char* who) {
+  TORCH_CHECK(dq_route >= -1 && dq_route <= 1, who,
+              ": dq_route must be -1 (auto), 0 (recompute) or 1 (stored dS)");
+  if (dq_route == 0) return false;
+  const char* why = ds_route_refusal(B, H, Hkv, T, D, has_lo, has_drop);
+  if (dq_route == 1) {
+    TORCH_CHECK(why == nullptr, who, ": dq_route=1: ", why);
+    return true;
+  }
+  return why == nullptr && sw_dq_ds();
+}
+
 // One launched instantiation.  Everything here comes from the template
 // arguments of the *_of() function that made it, so the kernel, its LDS size
 // and its reported name cannot disagree.
@@ -1253,10 +1464,12 @@ struct Variant {
   // MaxDynamicSharedMemorySize set for this instantiation?  nullptr: never
   // needed (forward and delta, < 64 KB)
   std::atomic<bool>* lds_raised;
-  // reported as stem<args...>, then ",1" for LO or ",0,1" for DROP
+  // reported as stem<args...>, then the LO, DROP, DSOUT flags up to the last
+  // one set: ",1" for LO, ",0,1" for DROP, ",0,0,1" for DSOUT
   const char* stem;
   int nargs, args[3];
   bool lo, drop;
+  bool dsout = false;
 };
 using FwdVariant = Variant<decltype(attn_fwd_kernel<64, false, false>)>;
 using DeltaVariant = Variant<decltype(attn_delta_kernel<64>)>;
@@ -1264,6 +1477,7 @@ using BwdVariant =
     Variant<decltype(attn_bwd_kernel<64, false, false, false, false>)>;
 using DqVariant =
     Variant<decltype(attn_dq_kernel<64, false, false, false, false>)>;
+using DqDsVariant = Variant<decltype(attn_dq_ds_kernel<256>)>;
 
 template <int D, bool LO, bool DROP = false>
 static FwdVariant fwd_v1_of() {
@@ -1280,13 +1494,14 @@ static DeltaVariant delta_of() {
   return {&attn_delta_kernel<D>, 0, 4, nullptr, "attn_delta_kernel", 1, {D},
           false, false};
 }
-template <int D, bool TR16, bool VL2, bool LO, bool DROP = false>
+template <int D, bool TR16, bool VL2, bool LO, bool DROP = false,
+          bool DSOUT = false>
 static BwdVariant bwd_of() {
   static std::atomic<bool> raised{false};
   constexpr bool HASV = (D <= 128) && !VL2;  // as in the kernel
-  return {&attn_bwd_kernel<D, TR16, VL2, LO, DROP>,
+  return {&attn_bwd_kernel<D, TR16, VL2, LO, DROP, DSOUT>,
           (int)sizeof(AttnBwdLdsT<D, HASV, LO>), bwd::KB, &raised,
-          "attn_bwd_kernel", 3, {D, TR16, VL2}, LO, DROP};
+          "attn_bwd_kernel", 3, {D, TR16, VL2}, LO, DROP, DSOUT};
 }
 template <int D, bool TR16, bool GKV, bool LO, bool DROP = false>
 static DqVariant dq_of() {
@@ -1294,6 +1509,12 @@ static DqVariant dq_of() {
   return {&attn_dq_kernel<D, TR16, GKV, LO, DROP>,
           (int)sizeof(AttnDqLds<D, GKV>), dq::QB, &raised, "attn_dq_kernel", 3,
           {D, TR16, GKV}, LO, DROP};
+}
+
+template <int D>
+static DqDsVariant dq_ds_of() {
+  return {&attn_dq_ds_kernel<D>, (int)sizeof(AttnDqDsLds<D>), dqds::QB,
+          nullptr, "attn_dq_ds_kernel", 1, {D}, false, false};
 }
 
 // f(D as a compile-time constant); D is one of 64, 128, 256 by now.
@@ -1348,11 +1569,23 @@ static DqVariant dq_variant(const AttnPlan& p, int D) {
   });
 }
 
+// The stored-dS route (use_ds_route decided it): the only instantiations are
+// the plain D = 256 pair.
+static BwdVariant bwd_ds_variant() {
+  return bwd_of<256, false, false, false, false, true>();
+}
+static DqDsVariant dq_ds_variant() { return dq_ds_of<256>(); }
+
 template <class Fn>
 static std::string name_of(const Variant<Fn>& v) {
   std::string s = std::string(v.stem) + "<" + std::to_string(v.args[0]);
   for (int i = 1; i < v.nargs; ++i) s += "," + std::to_string(v.args[i]);
-  return s + (v.drop ? ",0,1>" : v.lo ? ",1>" : ">");
+  const bool flags[3] = {v.lo, v.drop, v.dsout};
+  int last = -1;
+  for (int i = 0; i < 3; ++i)
+    if (flags[i]) last = i;
+  for (int i = 0; i <= last; ++i) s += flags[i] ? ",1" : ",0";
+  return s + ">";
 }
 
 // The kernel instantiations attn_fwd / attn_bwd launch for a padded T and
@@ -1360,11 +1593,21 @@ static std::string name_of(const Variant<Fn>& v) {
 // has_lo: the instantiations taken when a kv_lo bound is given (the names
 // then carry the LO template argument).  has_drop: those taken with
 // dropout_p > 0 (the names carry LO = 0 and the DROP argument).
-std::string attn_dispatch(int64_t T, int64_t D, bool has_lo, bool has_drop) {
+// ds_route: the backward names of the stored-dS dQ route, which attn_bwd
+// takes by default when B*H (not known here) keeps the scratch within
+// DS_SCRATCH_MAX_BYTES; an error if (T, D) and the flags are not eligible
+// even at B*H = 1.
+std::string attn_dispatch(int64_t T, int64_t D, bool has_lo, bool has_drop,
+                          bool ds_route) {
   TORCH_CHECK(T > 0 && T % QBLK == 0, "attn_dispatch: T must be a multiple of 64");
   TORCH_CHECK(D == 64 || D == 128 || D == 256, "attn_dispatch: D in {64,128,256}");
   const int d = (int)D;
   const AttnPlan p = attn_plan((int)T, d, has_lo, /*bwd=*/true, has_drop);
+  if (ds_route) {
+    use_ds_route(1, 1, 1, 1, T, D, has_lo, has_drop, "attn_dispatch");
+    return name_of(fwd_variant(p, d)) + " " + name_of(delta_variant(d)) + " " +
+           name_of(bwd_ds_variant()) + " " + name_of(dq_ds_variant());
+  }
   return name_of(fwd_variant(p, d)) + " " + name_of(delta_variant(d)) + " " +
          name_of(bwd_variant(p, d)) + " " + name_of(dq_variant(p, d));
 }
@@ -1511,7 +1754,9 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  at::Tensor v, at::Tensor o, at::Tensor lse,
                                  bool causal, int64_t kv_len,
                                  c10::optional<at::Tensor> kv_lo,
-                                 double dropout_p, int64_t seed) {
+                                 double dropout_p, int64_t seed,
+                                 int64_t dq_route,
+                                 c10::optional<at::Tensor> ds_scratch) {
   const auto [B, H, Hkv, T, D] = check_qkv(q, k, v, kv_len, "attn_bwd");
   TORCH_CHECK(dout.sizes() == q.sizes(), "attn_bwd: dout must have q's sizes");
   TORCH_CHECK(o.sizes() == q.sizes(), "attn_bwd: o must have q's sizes");
@@ -1530,6 +1775,18 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
   const DropArg dr = drop_arg(dropout_p, seed, q, "attn_bwd");
   const AttnPlan plan =
       attn_plan(T, D, lo.ptr != nullptr, /*bwd=*/true, dr.thr != 0);
+  const bool ds_route = use_ds_route(dq_route, B, H, Hkv, T, D,
+                                     lo.ptr != nullptr, dr.thr != 0, "attn_bwd");
+  const int64_t ds_numel = (int64_t)B * H * T * T;
+  if (ds_scratch.has_value()) {
+    const at::Tensor& s = *ds_scratch;
+    TORCH_CHECK(bf16_on(s, q), "attn_bwd: ds_scratch must be bf16 on q's device");
+    TORCH_CHECK(s.is_contiguous(), "attn_bwd: ds_scratch must be contiguous");
+    TORCH_CHECK(s.numel() >= ds_numel, "attn_bwd: ds_scratch must hold at "
+                "least B*H*T*T = ", ds_numel, " elements, got ", s.numel());
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(s.data_ptr()) & 15) == 0,
+                "attn_bwd: ds_scratch must be 16-B aligned");
+  }
 
   auto delta = at::empty({B, H, T}, q.options().dtype(at::kFloat));
   // grads physically [B, T, H, D] (matches the projection layout upstream,
@@ -1553,6 +1810,23 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
   launch(delta_variant(D), dim3(std::min((T + 3) / 4, 2048), B * H), stream,
          bf16_in(dout), bf16_in(o), delta.data_ptr<float>(), T, H,
          str_of(dout), str_of(o));
+  if (ds_route) {
+    // delta, dK/dV (which stores dS), dQ from the stored dS.  The scratch is
+    // never filled: attn_dq_ds_kernel reads only what the dK/dV blocks wrote.
+    at::Tensor ds = ds_scratch.has_value() ? *ds_scratch
+                                           : at::empty({ds_numel}, q.options());
+    const BwdVariant bv = bwd_ds_variant();
+    launch(bv, dim3(B * H, T / bv.rows), stream, bf16_in(dout), bf16_in(q),
+           bf16_in(k), bf16_in(v), lse.data_ptr<float>(),
+           delta.data_ptr<float>(), bf16_out(dk), bf16_out(dv), (float*)nullptr,
+           (float*)nullptr, T, H, Hkv, scale, c, kvl, str_of(dout), str_of(q),
+           str_of(k), str_of(v), str_of(dk), str_of(dv), lo.ptr, lo.sb,
+           dr.seed, dr.thr, dr.r, bf16_out(ds));
+    const DqDsVariant qv = dq_ds_variant();
+    launch(qv, dim3(B * H, T / qv.rows), stream, bf16_in(ds), bf16_in(k),
+           bf16_out(dq), T, H, c, str_of(k), str_of(dq));
+    return {dq, dk, dv};
+  }
   const DqVariant qv = dq_variant(plan, D);
   launch(qv, dim3(B * H, T / qv.rows), stream, bf16_in(dout), bf16_in(q),
          bf16_in(k), bf16_in(v), lse.data_ptr<float>(),
@@ -1567,7 +1841,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
          gqa ? dv_f32.data_ptr<float>() : nullptr, T, H, Hkv, scale, c, kvl,
          str_of(dout), str_of(q), str_of(k), str_of(v),
          gqa ? str_of(dk_f32) : str_of(dk), gqa ? str_of(dv_f32) : str_of(dv),
-         lo.ptr, lo.sb, dr.seed, dr.thr, dr.r);
+         lo.ptr, lo.sb, dr.seed, dr.thr, dr.r, (unsigned short*)nullptr);
   if (gqa) return {dq, dk_f32.to(at::kBFloat16), dv_f32.to(at::kBFloat16)};
   return {dq, dk, dv};
 }

@@ -60,9 +60,14 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  at::Tensor v, at::Tensor o, at::Tensor lse,
                                  bool causal, int64_t kv_len,
                                  c10::optional<at::Tensor> kv_lo,
-                                 double dropout_p = 0.0, int64_t seed = 0);
+                                 double dropout_p = 0.0, int64_t seed = 0,
+                                 int64_t dq_route = -1,
+                                 c10::optional<at::Tensor> ds_scratch =
+                                     c10::nullopt);
 std::string attn_dispatch(int64_t T, int64_t D, bool has_lo = false,
-                          bool has_drop = false);
+                          bool has_drop = false, bool ds_route = false);
+bool attn_ds_eligible(int64_t B, int64_t H, int64_t Hkv, int64_t T, int64_t D,
+                      bool has_lo, bool has_drop);
 
 // add3.hip, swiglu.hip, embedding.hip, dropout.hip
 at::Tensor add3(at::Tensor a, at::Tensor b, at::Tensor c);
