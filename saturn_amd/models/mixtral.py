@@ -23,7 +23,13 @@ from saturn_amd.ops.functional import (
     fused_cross_entropy,
     fused_swiglu,
 )
-from saturn_amd.ops.moe import moe_combine, moe_permute, moe_route, moe_sort
+from saturn_amd.ops.moe import (
+    moe_combine,
+    moe_grouped_linear,
+    moe_permute,
+    moe_route,
+    moe_sort,
+)
 
 
 @dataclass
@@ -81,6 +87,28 @@ def route(router: nn.Linear, x_flat: torch.Tensor, top_k: int):
     return topv.to(x_flat.dtype), topi
 
 
+def _grouped_expert_weights(experts):
+    """(gate, up, down) weight lists for ``dispatch="grouped"``, which
+    multiplies by the raw matrices and so cannot honour anything else an
+    expert module might do."""
+    for e, expert in enumerate(experts):
+        ok = type(expert) is MoEExpert and all(
+            type(lin) is nn.Linear and lin.bias is None
+            for lin in (expert.gate_proj, expert.up_proj, expert.down_proj)
+        )
+        if not ok:
+            raise TypeError(
+                'MoE dispatch "grouped" needs experts that are exactly '
+                "MoEExpert with plain bias-free nn.Linear projections; "
+                f"expert {e} is {type(expert).__name__}"
+            )
+    return (
+        [expert.gate_proj.weight for expert in experts],
+        [expert.up_proj.weight for expert in experts],
+        [expert.down_proj.weight for expert in experts],
+    )
+
+
 def moe_experts_forward(xf, weights, ids, experts, dispatch):
     """The expert stage of one MoE layer, given a routing result: returns
     ``out[t] = sum_j weights[t,j] * experts[ids[t,j]](xf[t])`` as [N, hidden].
@@ -94,7 +122,23 @@ def moe_experts_forward(xf, weights, ids, experts, dispatch):
     in fp32 (``moe_combine``).  It keeps ONE host sync per layer (the
     ``counts.tolist()`` that sizes the slices), so like the loop path it
     cannot be captured into a hipGraph.
+
+    ``dispatch="grouped"`` keeps the sort, permute and combine of ``"fused"``
+    and replaces the per-expert slices by ``moe_grouped_linear``: the gate,
+    up and down projections of ALL experts are one grouped GEMM each (three
+    launches forward, six backward, whatever E is) around one ``fused_swiglu``
+    over the whole [N*k, ffn].  The kernels read ``counts`` on the device, so
+    there is no host sync and the layer can be captured into a hipGraph.  It
+    needs experts that are exactly :class:`MoEExpert` with plain bias-free
+    ``nn.Linear`` children.
     """
+    if dispatch == "grouped":
+        gate_w, up_w, down_w = _grouped_expert_weights(experts)
+        order, pos, counts = moe_sort(ids, len(experts))
+        xs = moe_permute(xf, order, pos)
+        h = fused_swiglu(moe_grouped_linear(xs, counts, gate_w),
+                         moe_grouped_linear(xs, counts, up_w))
+        return moe_combine(moe_grouped_linear(h, counts, down_w), weights, pos)
     if dispatch == "loop":
         out = torch.zeros_like(xf)
         for e, expert in enumerate(experts):
@@ -128,8 +172,10 @@ def resolve_dispatch(dispatch, x: torch.Tensor) -> str:
 class MoEMLP(nn.Module):
     """Dense-dispatch reference MoE layer (single process, exact).
 
-    ``dispatch``: ``"loop"``, ``"fused"`` or ``None`` (auto: ``"fused"`` on
-    GPU, ``"loop"`` on CPU) — see :func:`moe_experts_forward`.
+    ``dispatch``: ``"loop"``, ``"fused"``, ``"grouped"`` or ``None`` (auto:
+    ``"fused"`` on GPU, ``"loop"`` on CPU) — see :func:`moe_experts_forward`.
+    ``"grouped"`` is opt-in: the only dispatch without a host sync, so the
+    only one that runs under a captured hipGraph.
     """
 
     def __init__(self, cfg: MixtralConfig):

@@ -48,9 +48,11 @@ def require_ext():
     return ext
 
 
-# MoE routing / dispatch ops (K13); imported last: ops.moe needs require_ext
+# MoE routing / dispatch ops (K13) and grouped expert GEMMs (K17); imported
+# last: ops.moe needs require_ext
 from saturn_amd.ops.moe import (  # noqa: E402
     moe_combine,
+    moe_grouped_linear,
     moe_permute,
     moe_route,
     moe_sort,
@@ -63,4 +65,5 @@ __all__ = [
     "moe_sort",
     "moe_permute",
     "moe_combine",
+    "moe_grouped_linear",
 ]

@@ -71,6 +71,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "weighted sum of each token's k expert rows");
   m.def("moe_combine_bwd", &samd::moe_combine_bwd,
         "combine backward: dy and fp32 dweights");
+  m.def("moe_gemm_fwd", &samd::moe_gemm_fwd,
+        "grouped expert GEMM: Y = xs @ W_e^T per segment of counts",
+        py::arg("xs"), py::arg("counts"), py::arg("weights"));
+  m.def("moe_gemm_dx", &samd::moe_gemm_dx,
+        "grouped expert GEMM: dX = dY @ W_e per segment of counts",
+        py::arg("dy"), py::arg("counts"), py::arg("weights"));
+  m.def("moe_gemm_dw", &samd::moe_gemm_dw,
+        "grouped expert GEMM: dW[e] = dY_e^T @ xs_e, [E, Nout, K]",
+        py::arg("dy"), py::arg("xs"), py::arg("counts"));
   m.def("mlp_act_bwd", &samd::mlp_act_bwd,
         "GELU backward + transposed d_pre / gelu(pre) + fp32 bias grad",
         py::arg("d_act"), py::arg("pre"), py::arg("want_dT") = true,

@@ -91,6 +91,13 @@ at::Tensor moe_combine_fwd(at::Tensor y, at::Tensor weights, at::Tensor pos);
 std::vector<at::Tensor> moe_combine_bwd(at::Tensor dout, at::Tensor y,
                                         at::Tensor weights, at::Tensor pos);
 
+// moe_gemm.hip
+at::Tensor moe_gemm_fwd(at::Tensor xs, at::Tensor counts,
+                        std::vector<at::Tensor> weights);
+at::Tensor moe_gemm_dx(at::Tensor dy, at::Tensor counts,
+                       std::vector<at::Tensor> weights);
+at::Tensor moe_gemm_dw(at::Tensor dy, at::Tensor xs, at::Tensor counts);
+
 // mlp_bwd.hip
 std::vector<at::Tensor> mlp_act_bwd(at::Tensor d_act, at::Tensor pre,
                                     bool want_dT, bool want_aT);

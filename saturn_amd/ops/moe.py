@@ -1,4 +1,5 @@
-"""MoE routing and token dispatch ops (K13) with pure-torch fallbacks.
+"""MoE routing and token dispatch ops (K13) and the grouped expert GEMMs
+(K17), with pure-torch fallbacks.
 
 Four ops cover everything around the expert GEMMs of the Mixtral path:
 
@@ -6,6 +7,9 @@ Four ops cover everything around the expert GEMMs of the Mixtral path:
 ``moe_sort``     stable counting sort of the (token, slot) pairs by expert
 ``moe_permute``  gather token rows into expert order
 ``moe_combine``  weighted sum of each token's k expert rows
+
+and ``moe_grouped_linear`` is the expert GEMMs themselves: one linear layer
+of every expert over the permuted rows, sized by ``counts`` on the device.
 
 GPU tensors inside the kernels' envelope (``n_expert <= 64``,
 ``top_k <= min(8, n_expert)``, ``hidden % 8 == 0``, rows in bf16/fp16/fp32,
@@ -203,3 +207,95 @@ def moe_combine(
     rows = y.index_select(0, pos.reshape(-1).long()).view(n, top_k, -1)
     out = (rows.float() * weights.float().unsqueeze(-1)).sum(dim=1)
     return out.to(y.dtype)
+
+
+# ---------------------------------------------------------------------------
+# grouped expert GEMMs (K17)
+# ---------------------------------------------------------------------------
+class _GroupedLinearFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xs, counts, *weights):
+        ext = require_ext()
+        y = ext.moe_gemm_fwd(xs, counts, list(weights))
+        ctx.save_for_backward(xs, counts, *weights)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = require_ext()
+        xs, counts, *weights = ctx.saved_tensors
+        dy = dy.contiguous()
+        if dy.data_ptr() % 16:  # the kernels stage rows as 16-B vectors
+            dy = dy.clone()
+        dxs = dws = None
+        if ctx.needs_input_grad[0]:
+            dxs = ext.moe_gemm_dx(dy, counts, weights)
+        if any(ctx.needs_input_grad[2:]):
+            dws = ext.moe_gemm_dw(dy, xs, counts).unbind(0)
+        else:
+            dws = (None,) * len(weights)
+        return (dxs, None, *dws)
+
+
+def _grouped_linear_torch(xs, counts, weights):
+    # segment loop; fp32 matmul, one rounding.  An empty expert multiplies a
+    # [0, K] slice, which leaves its weight a zero gradient.
+    pieces = [
+        (rows.float() @ w.float().t()).to(xs.dtype)
+        for rows, w in zip(xs.split(counts.tolist()), weights)
+    ]
+    return torch.cat(pieces)
+
+
+def _grouped_ok(xs, counts, weights) -> bool:
+    w0 = weights[0]
+    return (
+        xs.is_cuda
+        and xs.data_ptr() % 16 == 0
+        and xs.dtype == torch.bfloat16
+        and xs.dim() == 2
+        and xs.shape[0] > 0
+        and xs.is_contiguous()
+        and counts.device == xs.device
+        and counts.dtype == torch.int32
+        and counts.shape == (len(weights),)
+        and 1 <= len(weights) <= MAX_EXPERTS
+        and w0.dim() == 2
+        and w0.shape[0] % 32 == 0
+        and w0.shape[1] % 32 == 0
+        and w0.shape[1] == xs.shape[1]
+        and all(
+            w.dtype == torch.bfloat16
+            and w.device == xs.device
+            and w.shape == w0.shape
+            and w.is_contiguous()
+            and w.data_ptr() % 16 == 0
+            for w in weights
+        )
+    )
+
+
+def moe_grouped_linear(xs: torch.Tensor, counts: torch.Tensor, weights):
+    """``y[r] = xs[r] @ weights[e].T`` for the rows r of segment e: rows
+    ``xs`` [P, K] in expert order (as :func:`moe_permute` leaves them),
+    segment e being the ``counts[e]`` rows after those of the experts before
+    it, and ``weights`` a sequence of E separate [Nout, K] matrices (the
+    experts' ``nn.Linear.weight``).  Returns [P, Nout]; fp32 accumulation,
+    one rounding.  Differentiable in ``xs`` and every weight; an expert
+    without rows gets a zero gradient.  ``sum(counts) == P`` is the caller's
+    to keep (``moe_sort`` does).
+
+    bf16 GPU rows with ``K % 32 == 0``, ``Nout % 32 == 0`` and at most 64
+    experts (bf16 weights of one shape, int32 ``counts``, all contiguous,
+    16-byte aligned and on one device) run as one grouped MFMA GEMM launch forward and two backward
+    (``moe_gemm.hip``, K17) that read ``counts`` on the device: no host sync.
+    Everything else (CPU, other dtypes or shapes) is a torch segment loop
+    over ``counts.tolist()``.
+    """
+    weights = tuple(weights)
+    if not weights:
+        raise ValueError("moe_grouped_linear: weights must hold at least "
+                         "one matrix")
+    if _grouped_ok(xs, counts, weights):
+        return _GroupedLinearFn.apply(xs, counts, *weights)
+    return _grouped_linear_torch(xs, counts, weights)

@@ -1,14 +1,17 @@
 """One MoEMLP layer, forward + backward, at the 8x7b-proxy shape (hidden
 2048, ffn 4096, 8 experts, top-2, N = 8192 tokens, bf16): the per-expert
-loop dispatch against the fused kernels (moe.hip, K13) in one process,
-alternating, so both see the same machine state.
+loop dispatch, the fused kernels (moe.hip, K13) and the grouped expert GEMMs
+(moe_gemm.hip, K17) in one process, alternating, so all see the same machine
+state.
 
 Every number is a host clock around a window of `--repeats` calls that ends
 in a device synchronise; the table gives median and spread (min..max) over
 `--windows` windows per path after warm-up.  Besides the whole layer it
 times the forward of the routing stage alone (torch chain vs `moe_route`,
-both from the router's logits) and of the dispatch stages alone (permute +
-combine around identity experts) on both paths.
+both from the router's logits), of the dispatch stages alone (permute +
+combine around identity experts) on both paths, and each grouped GEMM kernel
+alone against the per-expert torch matmuls it replaces, at the layer's two
+GEMM shapes and its routing (TF/s = 2 P K Nout / median time).
 
     python tools/moe_bench.py [--tokens 8192] [--windows 10] [--repeats 5]
 
@@ -124,12 +127,15 @@ def main() -> None:
           f"{args.repeats} calls then a synchronise; ms per call")
     print(f"{'':<34} {'median':>9} {'min':>9} {'max':>9} {'spread':>9}")
 
-    res = windows({"loop": layer_step("loop"), "fused": layer_step("fused")},
+    res = windows({d: layer_step(d) for d in ("loop", "fused", "grouped")},
                   args.windows, args.repeats, args.warmup)
     line, med_loop, sp_loop = row("layer fwd+bwd, dispatch=loop", res["loop"])
     print(line)
     line, med_fused, sp_fused = row("layer fwd+bwd, dispatch=fused",
                                     res["fused"])
+    print(line)
+    line, med_grouped, sp_grouped = row("layer fwd+bwd, dispatch=grouped",
+                                        res["grouped"])
     print(line)
 
     res = windows(
@@ -147,11 +153,45 @@ def main() -> None:
     print(row("dispatch fwd (identity), loop", res["loop"])[0])
     print(row("dispatch fwd (identity), fused", res["fused"])[0])
 
+    ext = require_ext()
+    cnt = torch.tensor(counts, dtype=torch.int32, device=dev)
+    P = N * cfg.top_k
+    for shape, K, Nout in (("gate/up", H, cfg.ffn_dim),
+                           ("down", cfg.ffn_dim, H)):
+        xs = torch.randn(P, K, device=dev, dtype=dt)
+        dy = torch.randn(P, Nout, device=dev, dtype=dt)
+        ws = [torch.randn(Nout, K, device=dev, dtype=dt) * 0.02
+              for _ in counts]
+        xe, de = xs.split(counts), dy.split(counts)
+        pairs = {
+            "fwd": (lambda: ext.moe_gemm_fwd(xs, cnt, ws),
+                    lambda: [x @ w.t() for x, w in zip(xe, ws)]),
+            "dx": (lambda: ext.moe_gemm_dx(dy, cnt, ws),
+                   lambda: [d @ w for d, w in zip(de, ws)]),
+            "dw": (lambda: ext.moe_gemm_dw(dy, xs, cnt),
+                   lambda: [d.t() @ x for d, x in zip(de, xe)]),
+        }
+        for op, (grouped, per_expert) in pairs.items():
+            res = windows({"moe_gemm": no_grad(grouped),
+                           "per-expert matmul": no_grad(per_expert)},
+                          args.windows, args.repeats * 4, args.warmup)
+            for arm, ms in res.items():
+                line, med, _ = row(f"{op} {shape}, {arm}", ms)
+                print(f"{line} {2.0 * P * K * Nout / med / 1e9:7.1f} TF/s")
+
     spread = max(sp_loop, sp_fused)
     gain = med_loop - med_fused
     verdict = "fused is faster" if gain > spread else "no gain beyond spread"
     print(f"layer fwd+bwd: loop - fused = {gain:.3f} ms "
           f"({gain / med_loop * 100:.1f} % of loop), run-to-run spread "
+          f"{spread:.3f} ms -> {verdict}")
+    spread = max(sp_fused, sp_grouped)
+    gain = med_fused - med_grouped
+    verdict = ("grouped is faster" if gain > spread else
+               "grouped is slower" if -gain > spread else
+               "no difference beyond spread")
+    print(f"layer fwd+bwd: fused - grouped = {gain:.3f} ms "
+          f"({gain / med_fused * 100:.1f} % of fused), run-to-run spread "
           f"{spread:.3f} ms -> {verdict}")
 
 
