@@ -622,8 +622,14 @@ __global__ void attn_fwd_v2_kernel(const unsigned short* __restrict__ Q,
 //   attn_bwd_kernel    dK/dV.  Grid over kv tiles: each block owns 64 keys
 //                      (16 per wave), loops over q tiles of 32 rows and
 //                      accumulates dK/dV in registers across the loop; stored
-//                      once as bf16, or added to fp32 buffers with atomics
-//                      when several q heads share a kv head (GQA).
+//                      once as bf16.  When several q heads share a kv head
+//                      (GQA) either the block owns the key block for the
+//                      whole group and loops over its q heads (GROUP, the
+//                      group route: still one bf16 store, a fixed summation
+//                      order), or there is one block per q head and the
+//                      partials are added to fp32 buffers with atomics (the
+//                      atomic route: arrival order, no bitwise claim).
+//                      use_group_route() picks.
 //   attn_dq_kernel     dQ.  Grid over q blocks: each block owns 64 q rows,
 //                      loops over key tiles of 32 and accumulates dQ in
 //                      registers; stored once as bf16, no atomics.
@@ -707,7 +713,14 @@ __global__ void attn_delta_kernel(const unsigned short* __restrict__ dO,
 
 // DSOUT: also store the bf16 dS values (the ones written to lds.dst) into the
 // global scratch DS[bh][q][key], row length T, for attn_dq_ds_kernel.
-template <int D, bool TR16, bool VL2, bool LO, bool DROP, bool DSOUT = false>
+// GROUP: the block owns 64 keys of one KV head and loops over the
+// G = n_heads / n_kv q heads that share it (grid.x = B * n_kv).  K (and V)
+// are staged once, acc_dk / acc_dv run on through the head loop and are
+// stored once as bf16: no atomics, no fp32 buffers.  Every output element is
+// summed in one fixed order, heads ascending and q tiles ascending within a
+// head, so the result depends on nothing but the shapes.
+template <int D, bool TR16, bool VL2, bool LO, bool DROP, bool DSOUT = false,
+          bool GROUP = false>
 __launch_bounds__(256, 2)
 __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
                                 const unsigned short* __restrict__ Q,
@@ -728,6 +741,7 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
                                 float drop_r,
                                 unsigned short* __restrict__ DS) {
   using namespace bwd;
+  static_assert(!(GROUP && DSOUT), "the dS scratch is indexed by one q head");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool HASV = (D <= 128) && !VL2;  // V tile LDS-resident?
   AttnBwdLdsT<D, HASV, LO>& lds =
@@ -739,9 +753,16 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
   const int qg = lane >> 4;
   // bh fastest (see forward): spreads the causal kv-block imbalance
   const int kv0 = blockIdx.y * KB;
-  const long bh = blockIdx.x;
-  const long b = bh / n_heads, h = bh % n_heads;
-  const long h_kv = h * n_kv / n_heads;  // GQA: q heads share kv heads
+  // GROUP: blockIdx.x is b * n_kv + h_kv, and bh / h / the four per-q-head
+  // bases below are those of the group's first head until the head loop
+  // moves them on
+  const int n_grp = GROUP ? n_heads / n_kv : 1;
+  const long bx = blockIdx.x;
+  const long b = bx / (GROUP ? n_kv : n_heads);
+  const long h = GROUP ? (bx % n_kv) * n_grp : bx % n_heads;
+  long bh = GROUP ? b * n_heads + h : bx;
+  // GQA: q heads share kv heads
+  const long h_kv = GROUP ? bx % n_kv : h * n_kv / n_heads;
   const unsigned short* Qh = Q + b * qs.sb + h * qs.sh;
   const unsigned short* Kh = K + b * ks.sb + h_kv * ks.sh;
   const unsigned short* Vh = V + b * vs.sb + h_kv * vs.sh;
@@ -776,6 +797,14 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
   }
 
   const int q_start = causal ? kv0 : 0;
+  // head loop (one trip unless GROUP; its tail is behind the q loop).  A
+  // head's q loop ends either behind its trailing barrier or, on the LO
+  // break, in front of the staging barrier of an iteration that has not
+  // begun: both lie behind the last read of qt / dot / pt / dst, so the next
+  // head may stage behind its own first barrier.  n_grp and the break are
+  // block-uniform.
+  int g = 0;
+  do {
   for (int q0 = q_start; q0 < T; q0 += QT) {
     // kv_lo is non-decreasing: once a q tile's FIRST row starts past this
     // block's last key, no later row sees the block.  One uniform address,
@@ -907,15 +936,35 @@ __global__ void attn_bwd_kernel(const unsigned short* __restrict__ dO,
     // no atomics; this kernel now only accumulates dK/dV.)
     __syncthreads();
   }
+  if constexpr (GROUP) {  // on to the group's next q head
+    ++bh;
+    Qh += qs.sh;
+    dOh += dos.sh;
+    lse_h += T;
+    del_h += T;
+  }
+  } while (GROUP && ++g < n_grp);
 
   // ---- epilogue: write dK, dV.  With GQA (several q heads per kv head)
-  // the partials accumulate into fp32 buffers with atomics; otherwise a
-  // direct bf16 store.
+  // the partials accumulate into fp32 buffers with atomics unless the block
+  // owns the whole group (GROUP); otherwise a direct bf16 store.
   if constexpr (DROP) {
 #pragma unroll
     for (int dt = 0; dt < D / 16; ++dt) acc_dv[dt] *= drop_r;
   }
-  if (n_kv != n_heads) {
+  if constexpr (GROUP) {
+    unsigned short* dKh = dK + b * dks.sb + h_kv * dks.sh;
+    unsigned short* dVh = dV + b * dvs.sb + h_kv * dvs.sh;
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int key_glob = kv0 + wid * 16 + qg * 4 + reg;
+#pragma unroll
+      for (int dt = 0; dt < D / 16; ++dt) {
+        dKh[(long)key_glob * dks.st + dt * 16 + r] = f2us(acc_dk[dt][reg]);
+        dVh[(long)key_glob * dvs.st + dt * 16 + r] = f2us(acc_dv[dt][reg]);
+      }
+    }
+  } else if (n_kv != n_heads) {
     float* dKh = dKf + b * dks.sb + h_kv * dks.sh;
     float* dVh = dVf + b * dvs.sb + h_kv * dvs.sh;
 #pragma unroll
@@ -1374,6 +1423,7 @@ struct AttnPlan {
   bool gkv;     // dQ: K/V/Q/dO fragments from L2
   bool lo;      // the kv_lo instantiations
   bool drop;    // the attention-dropout instantiations
+  bool group;   // dK/dV: the group-owning instantiations (use_group_route)
 };
 // bwd: the plan will select backward kernels (attn_bwd, attn_dispatch).  The
 // kv_lo backward is built for the default switches only and refused by name
@@ -1402,7 +1452,7 @@ static AttnPlan attn_plan(int T, int D, bool has_lo, bool bwd = true,
   }
   return AttnPlan{sw_v2() && T % 128 == 0 && D <= 128, sw_tr16() && D <= 128,
                   sw_vl2() && D <= 128, sw_dq_gkv() && D > 128, has_lo,
-                  has_drop};
+                  has_drop, false};
 }
 
 // dQ from stored dS (attn_bwd_kernel<..., DSOUT> + attn_dq_ds_kernel) instead
@@ -1453,6 +1503,52 @@ static bool use_ds_route(int64_t dq_route, int64_t B, int64_t H, int64_t Hkv,
   return why == nullptr && sw_dq_ds();
 }
 
+// dK/dV under GQA by the group-owning kernel (attn_bwd_kernel<..., GROUP>:
+// one block per 64 keys of a KV head, looping over the group's q heads)
+// instead of one block per q head adding into fp32 buffers with atomics.
+// SAMD_ATTN_GQA_GROUP=0 keeps the atomic route for the whole process.
+static bool sw_gqa_group() {
+  static const bool v = !env_is("SAMD_ATTN_GQA_GROUP", '0');
+  return v;
+}
+// Smallest group-route grid (B * Hkv * T/64 blocks) auto takes: 3 blocks for
+// each of the 256 CUs.  From profiles/attn_gqa_group_bench.txt (H32 Hkv8 D128
+// causal, group / atomic backward time): every grid measured at 768 blocks
+// or more is faster (768: x0.91; 1024: x0.84, x0.91 with a window, x0.66),
+// at 512 blocks one shape of three loses (B2 T2048 x1.12) and at 256 both do
+// (B4 T512 x1.09, B1 T2048 x1.65): the group route has G times fewer blocks
+// and its time stays flat until they fill the device.
+constexpr int64_t GROUP_MIN_BLOCKS = 768;
+// The one place that decides the dK/dV route.  nullptr: the group kernels
+// are built for this process' switches (default TR16, V in LDS at D <= 128);
+// otherwise the switch that rules them out.
+static const char* group_route_refusal() {
+  if (!sw_tr16())
+    return "the group dK/dV route is not built for SAMD_ATTN_BWD_TR16=0; "
+           "unset the switch";
+  if (sw_vl2())
+    return "the group dK/dV route is not built for SAMD_ATTN_BWD_VL2=1; "
+           "unset the switch";
+  return nullptr;
+}
+// dkv_route: -1 auto, 0 atomic route (one block per q head; a direct store
+// when Hkv == H), 1 group route (an error if refused; G = 1 when Hkv == H).
+// Auto takes the group route for a GQA call it is built for when the grid
+// reaches GROUP_MIN_BLOCKS; smaller calls keep the atomic route.
+static bool use_group_route(int64_t dkv_route, int64_t B, int64_t H,
+                            int64_t Hkv, int64_t T, const char* who) {
+  TORCH_CHECK(dkv_route >= -1 && dkv_route <= 1, who,
+              ": dkv_route must be -1 (auto), 0 (atomic) or 1 (group)");
+  if (dkv_route == 0) return false;
+  const char* why = group_route_refusal();
+  if (dkv_route == 1) {
+    TORCH_CHECK(why == nullptr, who, ": dkv_route=1: ", why);
+    return true;
+  }
+  return Hkv != H && why == nullptr && sw_gqa_group() &&
+         B * Hkv * (T / bwd::KB) >= GROUP_MIN_BLOCKS;
+}
+
 // One launched instantiation.  Everything here comes from the template
 // arguments of the *_of() function that made it, so the kernel, its LDS size
 // and its reported name cannot disagree.
@@ -1464,12 +1560,14 @@ struct Variant {
   // MaxDynamicSharedMemorySize set for this instantiation?  nullptr: never
   // needed (forward and delta, < 64 KB)
   std::atomic<bool>* lds_raised;
-  // reported as stem<args...>, then the LO, DROP, DSOUT flags up to the last
-  // one set: ",1" for LO, ",0,1" for DROP, ",0,0,1" for DSOUT
+  // reported as stem<args...>, then the LO, DROP, DSOUT, GROUP flags up to
+  // the last one set: ",1" for LO, ",0,1" for DROP, ",0,0,1" for DSOUT,
+  // ",0,0,0,1" for GROUP
   const char* stem;
   int nargs, args[3];
   bool lo, drop;
   bool dsout = false;
+  bool group = false;
 };
 using FwdVariant = Variant<decltype(attn_fwd_kernel<64, false, false>)>;
 using DeltaVariant = Variant<decltype(attn_delta_kernel<64>)>;
@@ -1495,13 +1593,13 @@ static DeltaVariant delta_of() {
           false, false};
 }
 template <int D, bool TR16, bool VL2, bool LO, bool DROP = false,
-          bool DSOUT = false>
+          bool DSOUT = false, bool GROUP = false>
 static BwdVariant bwd_of() {
   static std::atomic<bool> raised{false};
   constexpr bool HASV = (D <= 128) && !VL2;  // as in the kernel
-  return {&attn_bwd_kernel<D, TR16, VL2, LO, DROP, DSOUT>,
+  return {&attn_bwd_kernel<D, TR16, VL2, LO, DROP, DSOUT, GROUP>,
           (int)sizeof(AttnBwdLdsT<D, HASV, LO>), bwd::KB, &raised,
-          "attn_bwd_kernel", 3, {D, TR16, VL2}, LO, DROP, DSOUT};
+          "attn_bwd_kernel", 3, {D, TR16, VL2}, LO, DROP, DSOUT, GROUP};
 }
 template <int D, bool TR16, bool GKV, bool LO, bool DROP = false>
 static DqVariant dq_of() {
@@ -1544,6 +1642,13 @@ static DeltaVariant delta_variant(int D) {
 static BwdVariant bwd_variant(const AttnPlan& p, int D) {
   return with_d(D, [&](auto d) -> BwdVariant {
     constexpr int DD = decltype(d)::value;
+    if (p.group) {  // default switches only (group_route_refusal)
+      if (p.lo)
+        return bwd_of<DD, (DD <= 128), false, true, false, false, true>();
+      if (p.drop)
+        return bwd_of<DD, (DD <= 128), false, false, true, false, true>();
+      return bwd_of<DD, (DD <= 128), false, false, false, false, true>();
+    }
     if (p.lo) return bwd_of<DD, (DD <= 128), false, true>();
     if (p.drop) return bwd_of<DD, (DD <= 128), false, false, true>();
     if constexpr (DD <= 128) {
@@ -1580,9 +1685,9 @@ template <class Fn>
 static std::string name_of(const Variant<Fn>& v) {
   std::string s = std::string(v.stem) + "<" + std::to_string(v.args[0]);
   for (int i = 1; i < v.nargs; ++i) s += "," + std::to_string(v.args[i]);
-  const bool flags[3] = {v.lo, v.drop, v.dsout};
+  const bool flags[4] = {v.lo, v.drop, v.dsout, v.group};
   int last = -1;
-  for (int i = 0; i < 3; ++i)
+  for (int i = 0; i < 4; ++i)
     if (flags[i]) last = i;
   for (int i = 0; i <= last; ++i) s += flags[i] ? ",1" : ",0";
   return s + ">";
@@ -1597,12 +1702,18 @@ static std::string name_of(const Variant<Fn>& v) {
 // takes by default when B*H (not known here) keeps the scratch within
 // DS_SCRATCH_MAX_BYTES; an error if (T, D) and the flags are not eligible
 // even at B*H = 1.
+// gqa: the backward names of the group dK/dV route (dkv_route=1), whatever
+// attn_bwd's auto rule would take at some B and Hkv; an error under a switch
+// the group kernels are not built for, or together with ds_route.
 std::string attn_dispatch(int64_t T, int64_t D, bool has_lo, bool has_drop,
-                          bool ds_route) {
+                          bool ds_route, bool gqa) {
   TORCH_CHECK(T > 0 && T % QBLK == 0, "attn_dispatch: T must be a multiple of 64");
   TORCH_CHECK(D == 64 || D == 128 || D == 256, "attn_dispatch: D in {64,128,256}");
   const int d = (int)D;
-  const AttnPlan p = attn_plan((int)T, d, has_lo, /*bwd=*/true, has_drop);
+  AttnPlan p = attn_plan((int)T, d, has_lo, /*bwd=*/true, has_drop);
+  TORCH_CHECK(!(gqa && ds_route), "attn_dispatch: the stored-dS dQ route "
+              "needs Hkv == H (no GQA)");
+  p.group = gqa && use_group_route(1, 1, 2, 1, T, "attn_dispatch");
   if (ds_route) {
     use_ds_route(1, 1, 1, 1, T, D, has_lo, has_drop, "attn_dispatch");
     return name_of(fwd_variant(p, d)) + " " + name_of(delta_variant(d)) + " " +
@@ -1756,7 +1867,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  c10::optional<at::Tensor> kv_lo,
                                  double dropout_p, int64_t seed,
                                  int64_t dq_route,
-                                 c10::optional<at::Tensor> ds_scratch) {
+                                 c10::optional<at::Tensor> ds_scratch,
+                                 int64_t dkv_route) {
   const auto [B, H, Hkv, T, D] = check_qkv(q, k, v, kv_len, "attn_bwd");
   TORCH_CHECK(dout.sizes() == q.sizes(), "attn_bwd: dout must have q's sizes");
   TORCH_CHECK(o.sizes() == q.sizes(), "attn_bwd: o must have q's sizes");
@@ -1773,10 +1885,15 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
               "attn_bwd: lse must be a contiguous [B, H, T] tensor");
   const LoArg lo = lo_arg(kv_lo, q, causal, "attn_bwd");
   const DropArg dr = drop_arg(dropout_p, seed, q, "attn_bwd");
-  const AttnPlan plan =
-      attn_plan(T, D, lo.ptr != nullptr, /*bwd=*/true, dr.thr != 0);
-  const bool ds_route = use_ds_route(dq_route, B, H, Hkv, T, D,
-                                     lo.ptr != nullptr, dr.thr != 0, "attn_bwd");
+  AttnPlan plan = attn_plan(T, D, lo.ptr != nullptr, /*bwd=*/true, dr.thr != 0);
+  plan.group = use_group_route(dkv_route, B, H, Hkv, T, "attn_bwd");
+  // the group kernel does not store dS: an explicit dkv_route=1 (the only
+  // way to the group route with Hkv == H) keeps the recompute dQ route
+  TORCH_CHECK(!(plan.group && dq_route == 1), "attn_bwd: dq_route=1 (stored "
+              "dS) is not built together with dkv_route=1");
+  const bool ds_route =
+      use_ds_route(dq_route, B, H, Hkv, T, D, lo.ptr != nullptr, dr.thr != 0,
+                   "attn_bwd") && !plan.group;
   const int64_t ds_numel = (int64_t)B * H * T * T;
   if (ds_scratch.has_value()) {
     const at::Tensor& s = *ds_scratch;
@@ -1793,7 +1910,9 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
   // so the model-side transposes stay views).  dQ is written exactly once
   // by the q-block dQ kernel: bf16 direct, no fp32 scratch, no zero-fill.
   auto dq = at::empty({B, T, H, D}, q.options()).permute({0, 2, 1, 3});
-  const bool gqa = Hkv != H;
+  // fp32 accumulation buffers, their fill and the casts at the end: the
+  // atomic route under GQA only
+  const bool gqa = Hkv != H && !plan.group;
   auto dk = at::empty({B, T, Hkv, D}, k.options()).permute({0, 2, 1, 3});
   auto dv = at::empty({B, T, Hkv, D}, v.options()).permute({0, 2, 1, 3});
   at::Tensor dk_f32, dv_f32;
@@ -1834,7 +1953,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
          str_of(dout), str_of(q), str_of(k), str_of(v), str_of(dq), lo.ptr,
          lo.sb, dr.seed, dr.thr, dr.r);
   const BwdVariant bv = bwd_variant(plan, D);
-  launch(bv, dim3(B * H, T / bv.rows), stream, bf16_in(dout), bf16_in(q),
+  launch(bv, dim3(B * (plan.group ? Hkv : H), T / bv.rows), stream,
+         bf16_in(dout), bf16_in(q),
          bf16_in(k), bf16_in(v), lse.data_ptr<float>(),
          delta.data_ptr<float>(), bf16_out(dk), bf16_out(dv),
          gqa ? dk_f32.data_ptr<float>() : nullptr,

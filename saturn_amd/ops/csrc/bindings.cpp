@@ -40,7 +40,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_dispatch", &samd::attn_dispatch,
         "kernel instantiations attn_fwd/attn_bwd launch for (padded T, D)",
         py::arg("T"), py::arg("D"), py::arg("has_lo") = false,
-        py::arg("has_drop") = false, py::arg("ds_route") = false);
+        py::arg("has_drop") = false, py::arg("ds_route") = false,
+        py::arg("gqa") = false);
   m.def("attn_ds_eligible", &samd::attn_ds_eligible,
         "is a call eligible for the stored-dS dQ route of attn_bwd?",
         py::arg("B"), py::arg("H"), py::arg("Hkv"), py::arg("T"), py::arg("D"),
@@ -50,7 +51,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("o"), py::arg("lse"), py::arg("causal"),
         py::arg("kv_len") = -1, py::arg("kv_lo") = py::none(),
         py::arg("dropout_p") = 0.0, py::arg("seed") = 0,
-        py::arg("dq_route") = -1, py::arg("ds_scratch") = py::none());
+        py::arg("dq_route") = -1, py::arg("ds_scratch") = py::none(),
+        py::arg("dkv_route") = -1);
   m.def("add3", &samd::add3, "fused 3-way residual add");
   m.def("swiglu_fwd", &samd::swiglu_fwd, "fused silu(gate)*up");
   m.def("swiglu_bwd", &samd::swiglu_bwd, "fused SwiGLU backward");

@@ -63,9 +63,11 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  double dropout_p = 0.0, int64_t seed = 0,
                                  int64_t dq_route = -1,
                                  c10::optional<at::Tensor> ds_scratch =
-                                     c10::nullopt);
+                                     c10::nullopt,
+                                 int64_t dkv_route = -1);
 std::string attn_dispatch(int64_t T, int64_t D, bool has_lo = false,
-                          bool has_drop = false, bool ds_route = false);
+                          bool has_drop = false, bool ds_route = false,
+                          bool gqa = false);
 bool attn_ds_eligible(int64_t B, int64_t H, int64_t Hkv, int64_t T, int64_t D,
                       bool has_lo, bool has_drop);
 
