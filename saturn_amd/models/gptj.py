@@ -34,6 +34,7 @@ from saturn_amd.ops.functional import (
     rope_tables,
     FusedDropout,
     FusedEmbedding,
+    LazyLogits,
     gptj_mlp,
     mlp_fused_supported,
     gptj_branches,
@@ -54,6 +55,9 @@ class GPTJConfig:
     # reference attn_pdrop (dropout on the softmax output), fused into the
     # attention kernels; 0.0 = today's path exactly
     attn_pdrop: float = 0.0
+    # training forward returns LazyLogits: the loss runs lm_head itself and
+    # never forms the [B*T, V] logits (ops.fused_linear_cross_entropy)
+    fused_lm_loss: bool = False
 
 
 class GPTJAttention(nn.Module):
@@ -236,6 +240,8 @@ class GPTJForCausalLM(nn.Module):
         for block in self.h:
             x = block(x)
         x = self.ln_f(x)
+        if self.training and getattr(self.cfg, "fused_lm_loss", False):
+            return LazyLogits(x, self.lm_head.weight, self.lm_head.bias)
         return self.lm_head(x)
 
 
@@ -288,6 +294,7 @@ def get_gptj_model(kwargs=None):
         embd_pdrop=kwargs.get("embd_pdrop", 0.0),
         resid_pdrop=kwargs.get("resid_pdrop", 0.0),
         attn_pdrop=kwargs.get("attn_pdrop", 0.0),
+        fused_lm_loss=kwargs.get("fused_lm_loss", False),
     )
     torch.manual_seed(kwargs.get("seed", 0))
     return GPTJForCausalLM(cfg)

@@ -19,6 +19,7 @@ from saturn_amd.ops.functional import (
     causal_attention,
     fused_cross_entropy,
     fused_swiglu,
+    LazyLogits,
     rope_tables,
     FusedEmbedding,
 )
@@ -38,6 +39,9 @@ class LlamaConfig:
     sliding_window: Optional[int] = None
     # attention dropout (not supported together with sliding_window)
     attn_pdrop: float = 0.0
+    # training forward returns LazyLogits: the loss runs lm_head itself and
+    # never forms the [B*T, V] logits (ops.fused_linear_cross_entropy)
+    fused_lm_loss: bool = False
 
 
 PRESETS = {
@@ -145,7 +149,10 @@ class LlamaForCausalLM(nn.Module):
         x = self.wte(input_ids)
         for block in self.h:
             x = block(x)
-        return self.lm_head(self.ln_f(x))
+        x = self.ln_f(x)
+        if self.training and getattr(self.cfg, "fused_lm_loss", False):
+            return LazyLogits(x, self.lm_head.weight, self.lm_head.bias)
+        return self.lm_head(x)
 
 
 class _LlamaEmbed(nn.Module):
@@ -184,7 +191,7 @@ def get_llama_model(kwargs=None):
 
     cfg = PRESETS[kwargs.get("preset", "8b")]
     for key in ("n_layer", "n_ctx", "vocab_size", "sliding_window",
-                "attn_pdrop"):
+                "attn_pdrop", "fused_lm_loss"):
         if key in kwargs:
             cfg = replace(cfg, **{key: kwargs[key]})
     torch.manual_seed(kwargs.get("seed", 0))

@@ -57,8 +57,15 @@ from saturn_amd.ops.moe import (  # noqa: E402
     moe_route,
     moe_sort,
 )
+# fused lm_head + cross-entropy (K18)
+from saturn_amd.ops.functional import (  # noqa: E402
+    LazyLogits,
+    fused_linear_cross_entropy,
+)
 
 __all__ = [
+    "LazyLogits",
+    "fused_linear_cross_entropy",
     "has_ext",
     "require_ext",
     "moe_route",

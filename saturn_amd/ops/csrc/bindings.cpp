@@ -82,6 +82,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gemm_dw", &samd::moe_gemm_dw,
         "grouped expert GEMM: dW[e] = dY_e^T @ xs_e, [E, Nout, K]",
         py::arg("dy"), py::arg("xs"), py::arg("counts"));
+  m.def("lce_fwd", &samd::lce_fwd,
+        "lm_head + cross-entropy forward without logits: {loss[N], lse[N]}",
+        py::arg("hidden"), py::arg("weight"), py::arg("bias"),
+        py::arg("targets"), py::arg("ignore_index") = -100);
+  m.def("lce_bwd", &samd::lce_bwd,
+        "lm_head + cross-entropy backward by vocabulary chunks: "
+        "{dh, dW[, dbias]}; chunk = 0 picks the width from the shapes",
+        py::arg("hidden"), py::arg("weight"), py::arg("bias"),
+        py::arg("targets"), py::arg("lse"), py::arg("gscale"),
+        py::arg("ignore_index") = -100, py::arg("chunk") = 0);
   m.def("mlp_act_bwd", &samd::mlp_act_bwd,
         "GELU backward + transposed d_pre / gelu(pre) + fp32 bias grad",
         py::arg("d_act"), py::arg("pre"), py::arg("want_dT") = true,

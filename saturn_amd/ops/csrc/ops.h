@@ -100,6 +100,16 @@ at::Tensor moe_gemm_dx(at::Tensor dy, at::Tensor counts,
                        std::vector<at::Tensor> weights);
 at::Tensor moe_gemm_dw(at::Tensor dy, at::Tensor xs, at::Tensor counts);
 
+// lm_loss.hip
+std::vector<at::Tensor> lce_fwd(at::Tensor hidden, at::Tensor weight,
+                                c10::optional<at::Tensor> bias,
+                                at::Tensor targets, int64_t ignore_index);
+std::vector<at::Tensor> lce_bwd(at::Tensor hidden, at::Tensor weight,
+                                c10::optional<at::Tensor> bias,
+                                at::Tensor targets, at::Tensor lse,
+                                at::Tensor gscale, int64_t ignore_index,
+                                int64_t chunk);
+
 // mlp_bwd.hip
 std::vector<at::Tensor> mlp_act_bwd(at::Tensor d_act, at::Tensor pre,
                                     bool want_dT, bool want_aT);

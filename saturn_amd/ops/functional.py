@@ -123,8 +123,14 @@ def fused_cross_entropy(
     """Causal-LM loss: mean CE of ``logits[:, :-1]`` vs ``targets[:, 1:]``
     (``shift=True``) without materializing shifted copies of the logits.
 
-    logits: [B, T, V]; targets: [B, T] int64.
+    logits: [B, T, V]; targets: [B, T] int64.  A ``LazyLogits`` goes to
+    ``fused_linear_cross_entropy`` instead, which never forms the logits.
     """
+    if isinstance(logits, LazyLogits):
+        return fused_linear_cross_entropy(
+            logits.hidden, logits.weight, logits.bias, targets,
+            shift=shift, ignore_index=ignore_index,
+        )
     B, T, V = logits.shape
     if logits.is_cuda:
         Tr = T - 1 if shift else T
@@ -140,6 +146,95 @@ def fused_cross_entropy(
         lg = logits.float().reshape(-1, V)
         tg = targets.reshape(-1)
     return F.cross_entropy(lg, tg, ignore_index=ignore_index)
+
+
+# ---------------------------------------------------------------------------
+# Fused lm_head + cross-entropy (K18, lm_loss.hip): loss and gradients
+# without a [B*T, V] logits or dlogits tensor
+# ---------------------------------------------------------------------------
+class LazyLogits:
+    """``lm_head`` not yet applied: what a model returns instead of logits
+    when the loss is to be fused with the head (``fused_lm_loss``)."""
+
+    __slots__ = ("hidden", "weight", "bias")
+
+    def __init__(self, hidden, weight, bias=None):
+        self.hidden = hidden
+        self.weight = weight
+        self.bias = bias
+
+    def materialize(self) -> torch.Tensor:
+        return F.linear(self.hidden, self.weight, self.bias)
+
+
+class _LceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hidden, weight, bias, tg, ignore_index, chunk):
+        ext = require_ext()
+        h2 = hidden.reshape(-1, hidden.shape[-1])
+        loss, lse = ext.lce_fwd(h2, weight, bias, tg, ignore_index)
+        valid = (tg != ignore_index).sum().clamp(min=1)
+        ctx.save_for_backward(hidden, weight, bias, tg, lse, valid)
+        ctx.ignore_index = ignore_index
+        ctx.chunk = chunk
+        return loss.sum() / valid.float()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ext = require_ext()
+        hidden, weight, bias, tg, lse, valid = ctx.saved_tensors
+        gscale = (grad_out.float() / valid.float()).reshape(1)
+        out = ext.lce_bwd(
+            hidden.reshape(-1, hidden.shape[-1]), weight, bias, tg, lse,
+            gscale, ctx.ignore_index, ctx.chunk,
+        )
+        dbias = out[2] if bias is not None else None
+        return out[0].view(hidden.shape), out[1], dbias, None, None, None
+
+
+def fused_linear_cross_entropy(
+    hidden: torch.Tensor,
+    weight: torch.Tensor,
+    bias=None,
+    targets: torch.Tensor = None,
+    shift: bool = True,
+    ignore_index: int = -100,
+    chunk=None,
+) -> torch.Tensor:
+    """Mean cross-entropy of ``F.linear(hidden, weight, bias)`` against
+    ``targets`` over the rows that are not ``ignore_index``, without the
+    logits: the forward keeps softmax statistics per row, the backward
+    recomputes logit tiles and holds one vocabulary chunk of dlogits
+    (``chunk`` columns, a multiple of 128; None picks it from the shapes).
+
+    hidden: [B, T, K] with targets [B, T], or [N, K] with targets [N] (one
+    sequence).  ``shift=True`` is the causal-LM loss: position t is scored
+    against targets[:, t + 1] and the last position is ignored.
+
+    bf16 CUDA inputs take the HIP kernels (K % 32 == 0); anything else is
+    ``F.linear`` followed by ``fused_cross_entropy``.
+    """
+    if targets is None:
+        raise TypeError("fused_linear_cross_entropy needs targets")
+    if hidden.dim() == 2:
+        hidden, targets = hidden.unsqueeze(0), targets.reshape(1, -1)
+    tensors = (hidden, weight) + (() if bias is None else (bias,))
+    if not all(t.is_cuda and t.dtype == torch.bfloat16 for t in tensors):
+        return fused_cross_entropy(
+            F.linear(hidden, weight, bias), targets, shift=shift,
+            ignore_index=ignore_index,
+        )
+    # the shift lives in the targets alone, so hidden stays a dense [B*T, K]
+    if shift:
+        tg = torch.full_like(targets, ignore_index)
+        tg[:, :-1] = targets[:, 1:]
+    else:
+        tg = targets
+    return _LceFn.apply(
+        hidden.contiguous(), weight.contiguous(),
+        None if bias is None else bias.contiguous(),
+        tg.contiguous().view(-1), ignore_index, chunk or 0,
+    )
 
 
 # ---------------------------------------------------------------------------

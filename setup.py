@@ -33,6 +33,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "dropout.hip"),
         os.path.join(CSRC, "moe.hip"),
         os.path.join(CSRC, "moe_gemm.hip"),
+        os.path.join(CSRC, "lm_loss.hip"),
         os.path.join(CSRC, "mlp_bwd.hip"),
         os.path.join(CSRC, "gptj_block_bwd.hip"),
     ],
