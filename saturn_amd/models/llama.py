@@ -7,6 +7,7 @@ Random-init weights, synthetic tokens (no network for checkpoints).
 
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Optional
 
@@ -20,6 +21,8 @@ from saturn_amd.ops.functional import (
     fused_cross_entropy,
     fused_swiglu,
     LazyLogits,
+    llama_mlp,
+    llama_mlp_supported,
     rope_tables,
     FusedEmbedding,
 )
@@ -42,6 +45,10 @@ class LlamaConfig:
     # training forward returns LazyLogits: the loss runs lm_head itself and
     # never forms the [B*T, V] logits (ops.fused_linear_cross_entropy)
     fused_lm_loss: bool = False
+    # the MLP as one autograd node whose backward (llama_mlp_bwd.hip) runs
+    # the three weight gradients as TN GEMMs and does not save the
+    # activation; SAMD_LLAMA_MLP_FUSED=0|1 overrides it
+    fused_mlp_bwd: bool = False
 
 
 PRESETS = {
@@ -109,8 +116,37 @@ class LlamaMLP(nn.Module):
         self.gate_proj = nn.Linear(cfg.n_embd, cfg.ffn_dim, bias=False)
         self.up_proj = nn.Linear(cfg.n_embd, cfg.ffn_dim, bias=False)
         self.down_proj = nn.Linear(cfg.ffn_dim, cfg.n_embd, bias=False)
+        self.fused_mlp_bwd = getattr(cfg, "fused_mlp_bwd", False)
+
+    @staticmethod
+    def _plain_linear(m) -> bool:
+        # exactly nn.Linear (tensor parallelism swaps in Column/RowParallel
+        # children) and no hooks that a direct use of the weights would skip
+        return type(m) is nn.Linear and not (
+            m._forward_hooks
+            or m._forward_pre_hooks
+            or m._backward_hooks
+            or m._backward_pre_hooks
+        )
+
+    def _use_fused(self, x) -> bool:
+        v = os.environ.get("SAMD_LLAMA_MLP_FUSED")
+        if not (self.fused_mlp_bwd if v is None else v != "0"):
+            return False
+        gp, up, dp = self.gate_proj, self.up_proj, self.down_proj
+        return (
+            x.is_cuda
+            and all(self._plain_linear(m) for m in (gp, up, dp))
+            and llama_mlp_supported(x, gp.weight, up.weight, dp.weight,
+                                    gp.bias, up.bias, dp.bias)
+        )
 
     def forward(self, x):
+        if self._use_fused(x):
+            # same forward calls; the backward (llama_mlp_bwd.hip) fuses the
+            # SwiGLU backward with the TN weight-gradient operands
+            return llama_mlp(x, self.gate_proj.weight, self.up_proj.weight,
+                             self.down_proj.weight)
         return self.down_proj(fused_swiglu(self.gate_proj(x), self.up_proj(x)))
 
 
@@ -191,7 +227,7 @@ def get_llama_model(kwargs=None):
 
     cfg = PRESETS[kwargs.get("preset", "8b")]
     for key in ("n_layer", "n_ctx", "vocab_size", "sliding_window",
-                "attn_pdrop", "fused_lm_loss"):
+                "attn_pdrop", "fused_lm_loss", "fused_mlp_bwd"):
         if key in kwargs:
             cfg = replace(cfg, **{key: kwargs[key]})
     torch.manual_seed(kwargs.get("seed", 0))

@@ -103,6 +103,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transpose_into", &samd::transpose_into,
         "bf16 transpose stored into a caller-given [N, M] view",
         py::arg("x"), py::arg("dst"));
+  m.def("swiglu_bwd_t", &samd::swiglu_bwd_t,
+        "SwiGLU backward + [d_gate^T; d_up^T] + regenerated silu(gate)*up: "
+        "{d_gate, d_up, dguT[2F,M], act ([F,M] with want_aT, else [M,F])}",
+        py::arg("d_act"), py::arg("gate"), py::arg("up"),
+        py::arg("want_guT") = true, py::arg("want_aT") = true);
+  m.def("llama_mlp_bwd", &samd::llama_mlp_bwd,
+        "Llama SwiGLU MLP backward with TN-layout weight gradients: "
+        "{dx, dW_gate, dW_up, dW_down}",
+        py::arg("g"), py::arg("x"), py::arg("gate"), py::arg("up"),
+        py::arg("W_gate"), py::arg("W_up"), py::arg("W_down"),
+        py::arg("tn_gu"), py::arg("tn_down"));
   m.def("rope_bwd_t", &samd::rope_bwd_t,
         "interleaved RoPE backward that also stores dx^T into a [E, M] view",
         py::arg("dy"), py::arg("cos"), py::arg("sin"), py::arg("t_len"),

@@ -119,6 +119,16 @@ std::vector<at::Tensor> mlp_bwd(at::Tensor g, at::Tensor h, at::Tensor pre,
                                 bool use_tn_in, bool use_tn_out);
 void transpose_into(at::Tensor x, at::Tensor dst);
 
+// llama_mlp_bwd.hip
+std::vector<at::Tensor> swiglu_bwd_t(at::Tensor d_act, at::Tensor gate,
+                                     at::Tensor up, bool want_guT,
+                                     bool want_aT);
+std::vector<at::Tensor> llama_mlp_bwd(at::Tensor g, at::Tensor x,
+                                      at::Tensor gate, at::Tensor up,
+                                      at::Tensor W_gate, at::Tensor W_up,
+                                      at::Tensor W_down, bool tn_gu,
+                                      bool tn_down);
+
 // gptj_block_bwd.hip
 at::Tensor rope_bwd_t(at::Tensor dy, at::Tensor cos_t, at::Tensor sin_t,
                       int64_t t_len, int64_t t_off, int64_t dim,

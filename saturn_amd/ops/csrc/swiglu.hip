@@ -8,14 +8,11 @@
 
 #include "common.h"
 #include "ops.h"
+#include "swiglu_math.h"
 
 namespace samd {
 
 typedef __attribute__((ext_vector_type(8))) short s8w;
-
-__device__ __forceinline__ float silu_f(float x) {
-  return x / (1.f + __expf(-x));
-}
 
 template <typename T>
 __global__ void swiglu_fwd_kernel(const T* __restrict__ gate,
@@ -69,10 +66,9 @@ __global__ void swiglu_bwd_kernel(const T* __restrict__ dout,
         const float g = us2f((unsigned short)vg[e]);
         const float u = us2f((unsigned short)vu[e]);
         const float go = us2f((unsigned short)vo[e]);
-        const float sig = 1.f / (1.f + __expf(-g));
-        // d silu(g)/dg = sig * (1 + g * (1 - sig))
-        odg[e] = (short)f2us(go * u * sig * (1.f + g * (1.f - sig)));
-        odu[e] = (short)f2us(go * g * sig);
+        const float sig = sigmoid_f(g);
+        odg[e] = (short)f2us(swiglu_dgate_f(go, g, u, sig));
+        odu[e] = (short)f2us(swiglu_dup_f(go, g, sig));
       }
       *reinterpret_cast<s8w*>(dgate + i * 8) = odg;
       *reinterpret_cast<s8w*>(dup + i * 8) = odu;

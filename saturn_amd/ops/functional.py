@@ -694,6 +694,92 @@ def fused_swiglu(gate, up):
     return torch.nn.functional.silu(gate) * up
 
 
+# ---------------------------------------------------------------------------
+# Llama SwiGLU MLP with a fused backward (llama_mlp_bwd.hip): the SwiGLU
+# backward also writes [d_gate^T; d_up^T] and (silu(gate) up)^T, so the three
+# weight gradients can run as TN GEMMs and the activation is not saved.
+# ---------------------------------------------------------------------------
+# Per-site default of the TN route, from profiles/llama_mlp_tn_probe.txt
+# (M = 8192, E = 4096, F = 14336; a site is on only where TN's median lies
+# below NT's min); SAMD_LLAMA_MLP_TN_GU / SAMD_LLAMA_MLP_TN_DOWN = 0|1
+# override it for A/B runs.
+#   gu    stacked [28672, M].[4096, M]^T 1171 us against two NT calls 1986 us
+#         (min 1975): on
+#   down  [4096, M].[14336, M]^T 629 us against NT 1004 us (min 997): on
+_LLAMA_MLP_TN_DEFAULT = {"gu": True, "down": True}
+
+
+def _llama_mlp_tn(site: str) -> bool:
+    v = os.environ.get("SAMD_LLAMA_MLP_TN_" + site.upper())
+    return _LLAMA_MLP_TN_DEFAULT[site] if v is None else v != "0"
+
+
+def llama_mlp_supported(x, w_gate, w_up, w_down,
+                        b_gate=None, b_up=None, b_down=None) -> bool:
+    """Inputs ``ext.llama_mlp_bwd`` accepts: CUDA bf16, no biases, token
+    count and both widths multiples of 8, consistent weight shapes."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() >= 2):
+        return False
+    if not (b_gate is None and b_up is None and b_down is None):
+        return False
+    if any(t.dtype != torch.bfloat16 or not t.is_cuda
+           for t in (w_gate, w_up, w_down)):
+        return False
+    E = x.shape[-1]
+    M = x.numel() // E if E else 0
+    F_ = w_gate.shape[0]
+    return (
+        M > 0
+        and w_gate.shape == (F_, E)
+        and w_up.shape == (F_, E)
+        and w_down.shape == (E, F_)
+        and M % 8 == 0
+        and E % 8 == 0
+        and F_ % 8 == 0
+    )
+
+
+class _LlamaMlpFn(torch.autograd.Function):
+    """down(silu(gate_proj x) * up_proj x).  The forward is the unfused
+    path's four calls in its order; it saves x, gate and up but not the
+    activation, which the backward regenerates inside the SwiGLU-backward
+    pass."""
+
+    @staticmethod
+    def forward(ctx, x, w_gate, w_up, w_down):
+        ext = require_ext()
+        gate = F.linear(x, w_gate).contiguous()
+        up = F.linear(x, w_up).contiguous()
+        out = F.linear(ext.swiglu_fwd(gate, up), w_down)
+        ctx.save_for_backward(x, gate, up, w_gate, w_up, w_down)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ext = require_ext()
+        x, gate, up, w_gate, w_up, w_down = ctx.saved_tensors
+        E = x.shape[-1]
+        Fd = gate.shape[-1]
+        dx, dw_gate, dw_up, dw_down = ext.llama_mlp_bwd(
+            g.contiguous().view(-1, E),
+            x.contiguous().view(-1, E),
+            gate.view(-1, Fd),
+            up.view(-1, Fd),
+            w_gate.contiguous(),
+            w_up.contiguous(),
+            w_down.contiguous(),
+            _llama_mlp_tn("gu"),
+            _llama_mlp_tn("down"),
+        )
+        return dx.view(x.shape), dw_gate, dw_up, dw_down
+
+
+def llama_mlp(x, w_gate, w_up, w_down):
+    """Llama MLP through the fused backward; callers check
+    ``llama_mlp_supported`` first."""
+    return _LlamaMlpFn.apply(x, w_gate, w_up, w_down)
+
+
 class _EmbedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, idx):

@@ -36,6 +36,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "lm_loss.hip"),
         os.path.join(CSRC, "mlp_bwd.hip"),
         os.path.join(CSRC, "gptj_block_bwd.hip"),
+        os.path.join(CSRC, "llama_mlp_bwd.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],

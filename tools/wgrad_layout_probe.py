@@ -26,6 +26,19 @@ rule:
     OUT    NT against TN at [E,E]; the TN side pays one transpose of o
            (g^T is shared with fc_out)
     ACCUM  mm + add_  against  addmm_ with beta = 1 at [M,E].[E,E]
+
+    python tools/wgrad_layout_probe.py --llama
+
+times only Llama-3-8B's three MLP weight gradients (E = 4096, F = 14336) at
+M = 8192, NT against TN, for the sites of llama_mlp_bwd.hip:
+
+    gate/up  [14336,M].[4096,M]^T   one projection's gradient
+    down     [4096,M].[14336,M]^T
+    gu       two NT calls against one stacked TN [28672,M].[4096,M]^T
+
+Arms alternate in one process: 10 windows of 5 calls each ending in a
+synchronise, median [min..max].  A site's TN default is on only where TN's
+median lies below NT's min.
 """
 
 from __future__ import annotations
@@ -43,7 +56,73 @@ FF = 16384
 SHAPES = [("fc_in ", FF, E), ("fc_out", E, FF)]
 
 
+def window_arms(fns, windows=10, calls=5):
+    """Alternating arms, `windows` windows of `calls` calls each ending in a
+    synchronise: {name: (median, min, max)} in us per call."""
+    import time
+
+    import torch
+
+    for _ in range(2):
+        for fn in fns.values():
+            fn()
+    t = {k: [] for k in fns}
+    for _ in range(windows):
+        for k, fn in fns.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                fn()
+            torch.cuda.synchronize()
+            t[k].append((time.perf_counter() - t0) / calls * 1e6)
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in t.items()}
+
+
+def fmt(r):
+    return f"{r[0]:9.1f} [{r[1]:.1f}..{r[2]:.1f}]"
+
+
+def llama_sites() -> None:
+    import torch
+    import torch.nn.functional as F
+
+    LF = 14336
+    torch.manual_seed(0)
+    print(f"Llama-3-8B MLP weight gradients, M={M} E={E} F={LF} bf16, "
+          f"10 windows x 5 calls, median [min..max] us")
+    x = torch.randn(M, E, device="cuda").bfloat16()
+    dg = torch.randn(M, LF, device="cuda").bfloat16()
+    du = torch.randn(M, LF, device="cuda").bfloat16()
+    xT = x.t().contiguous()
+    dgT = dg.t().contiguous()
+    dguT = torch.cat((dg, du), 1).t().contiguous()
+
+    def nt2():
+        dg.t() @ x
+        du.t() @ x
+
+    sites = [
+        ("gate/up", 1, {"NT": lambda: dg.t() @ x,
+                        "TN": lambda: F.linear(dgT, xT)}),
+        # the same operands the other way round: dW_down[E,F] = g^T act
+        ("down", 1, {"NT": lambda: x.t() @ dg,
+                     "TN": lambda: F.linear(xT, dgT)}),
+        ("gu", 2, {"NT": nt2, "TN": lambda: F.linear(dguT, xT)}),
+    ]
+    for site, n, fns in sites:
+        r = window_arms(fns)
+        fl = 2.0 * M * E * LF * n
+        print(f"{site}:")
+        for name in ("NT", "TN"):
+            print(f"  {name}  {fmt(r[name])}  {fl / r[name][0] / 1e6:6.0f} TF/s")
+        on = r["TN"][0] < r["NT"][1]
+        print(f"  TN / NT x{r['TN'][0] / r['NT'][0]:.3f}; TN median below NT "
+              f"min: {on} -> default {'TN' if on else 'NT'}", flush=True)
+
+
 def main() -> None:
+    if sys.argv[1:] == ["--llama"]:
+        return llama_sites()
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 15
     assert repeats >= 10
 
